@@ -26,7 +26,16 @@ torchrun WORLD_SIZE must equal --gpus (exit 2 otherwise); `bench.py --gpus N`
 without one starts the N ranks itself (torch.distributed.run as a child
 process, before this process touches the GPU).
 
-Prints ONE JSON line on rank 0 (the driver's contract), including:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline needs: it renders and uploads the frames, warms up, times the K
+steps, writes --dump-outputs DIR if asked (DIR/<name>.npy, float64: the
+timed pose log, the map points, the last frame's LK alignment; the same
+arguments give the same inputs, so two builds compare output for output) and
+prints the line (value, ms_per_step = milliseconds per timed step, the
+in-run HIP-event groups, the pose gather).  Every side measurement below
+runs with --full only; without it those entries are null.
+
+Prints ONE JSON line on rank 0 (the driver's contract), with --full including:
   roofline     — the HBM-bound image pass (pyramid),
                  HIP-event timed inside this run;
   cpu_baseline — the CPU oracle (single thread) on a bounded sample of the
@@ -96,7 +105,35 @@ def parse():
                     help="rank 0 writes every rank's timed pose log (the gather's result) to this .npz")
     ap.add_argument("--rig-steps", type=int, default=64,
                     help="timesteps of the 4-camera rig measurements (configs[4]: SVO rig and the reference-path photometric rig; 0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (roofline, per-kernel breakdown chunk, CPU baselines and "
+                         "parity, the other precision, init / host-ingest / configs[2] / stereo-VO / rig legs, "
+                         "profile evidence); without it only the headline's warm-up and timed steps run and the "
+                         "--no-* / --cpu-* / --rig-steps options have nothing to act on")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned after its last timed step to DIR/<name>.npy "
+                         "(float64): the timed pose log, the map points and the last frame's LK alignment")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_cpu = args.no_svo = args.no_other = args.no_init = args.no_host_ingest = args.no_config2 = True
+        args.rig_steps = 0
+    return args
+
+
+def dump_outputs(out_dir, rank_poses, points, alignment):
+    """--dump-outputs: the arrays a caller of the timed path holds after the
+    last timed step, one float64 .npy each (a few hundred kB in all):
+    poses[_rankR] (steps, 12) the timed frames' Tcw rows, points (n, 3) the
+    map, and the last frame's LK alignment per map point (keyframe index,
+    success flag, position before and after)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pk, sc, ub, ua = alignment
+    arrays = {"points": points, "align_keyframe": pk, "align_success": sc, "align_before": ub, "align_after": ua}
+    for r, p in enumerate(rank_poses):
+        arrays["poses" if r == 0 else f"poses_rank{r}"] = p
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def measure_svo(args, seq, left, right, d_left, d_right, W, H, log, n):
@@ -715,7 +752,8 @@ def main():
     from viso_amd.synth import Sequence
 
     W, H = args.width, args.height
-    n_break = args.batch  # one extra chunk after the timed region: per-kernel breakdown
+    # --full: one extra chunk after the timed region, the per-kernel breakdown
+    n_break = args.batch if args.full else 0
     # stereo initialisation (viso_set_stereo): frame 0's pair creates the map,
     # so the warmup ends in kRunning and every timed frame is a tracking frame
     # (a frame that fails to initialise extends the warmup, bounded below)
@@ -749,10 +787,16 @@ def main():
         source = f"KITTI {root}"
     else:
         seq = Sequence(W, H, seed=sequence_seed(rank))
+    # Only the stereo initialisation reads a right image (viso_process_frames_device),
+    # and it runs in the warm-up: a plain run on the synthetic sequence renders
+    # the right images of the frames the warm-up can reach and hands the
+    # tracking chunks past them no right pointer (rendering is most of a plain
+    # run's set-up time).  The --full legs read every right image.
+    n_right = n_total if (args.full or args.kitti) else max(args.warmup, 1) + warm_cap
     t0 = time.time()
     left = np.stack([seq.image(f, 0) for f in range(n_total)])
-    right = np.stack([seq.image(f, 1) for f in range(n_total)])
-    log(f"[rank {rank}] loaded {n_total} stereo pairs ({source}) in {time.time() - t0:.1f}s")
+    right = np.stack([seq.image(f, 1) for f in range(n_right)])
+    log(f"[rank {rank}] loaded {n_total} left / {n_right} right images ({source}) in {time.time() - t0:.1f}s")
     d_left = torch.from_numpy(left).to(f"cuda:{local}")
     d_right = torch.from_numpy(right).to(f"cuda:{local}")
     torch.cuda.synchronize()
@@ -772,7 +816,7 @@ def main():
         while f < f0 + n:
             m = min(args.batch, f0 + n - f)
             v.process_device(d_left.data_ptr() + f * frame_bytes,
-                             d_right.data_ptr() + f * frame_bytes, m, frame_bytes)
+                             d_right.data_ptr() + f * frame_bytes if f + m <= n_right else None, m, frame_bytes)
             f += m
 
     # ---------------------------------------------------------- warmup
@@ -816,6 +860,15 @@ def main():
     # every tracking frame pushes one pose (src/viso.cpp:137); any other timed
     # frame would be an initialisation frame
     tracking_timed = len(poses) - n_pose_before
+    if tracking_timed != steps and n_right < n_total:
+        # (a re-initialisation inside the timed frames would have wanted a right image)
+        log(f"[rank {rank}] error: {steps - tracking_timed} timed frame(s) were not tracking frames; "
+            "run with --full (every right image resident)")
+        sys.exit(3)
+    if rank == 0 and args.dump_outputs:
+        # before any other leg touches the context
+        dump_outputs(args.dump_outputs, gathered if distributed else [poses[n_pose_before:]],
+                     v.GetPoints(), v.alignment())
     gather = None
     if distributed:
         pg_backend = str(dist.get_backend())
@@ -835,15 +888,16 @@ def main():
         n_l, ms = v.ctx.timing(k)
         if n_l:
             timing[k] = {"launches": n_l, "avg_ms": ms / n_l, "total_ms": ms}
-    # per-kernel breakdown: one more chunk with every kernel group timed
+    # per-kernel breakdown (--full): one more chunk with every kernel group timed
     v.ctx.timing_enable(False)
-    v.ctx.timing_select(None)
-    v.ctx.timing_enable(True)
-    if n_break:
-        run(warm + steps, n_break)
-    v.synchronize()
+    if args.full:
+        v.ctx.timing_select(None)
+        v.ctx.timing_enable(True)
+        if n_break:
+            run(warm + steps, n_break)
+        v.synchronize()
     breakdown = {}
-    for k in ("pyramid", "direct", "lkalign"):
+    for k in ("pyramid", "direct", "lkalign") if args.full else ():
         n_l, ms = v.ctx.timing(k)
         n0 = timing.get(k, {}).get("launches", 0)
         ms0 = timing.get(k, {}).get("total_ms", 0.0)
@@ -852,7 +906,7 @@ def main():
     dims, total_bytes = viso_amd.pyramid_dims(W, H)
     algo_bytes_img = dims[0][0] * dims[0][1] + sum(w * h for w, h in dims[1:])
     roofline = None
-    if "pyramid" in timing:
+    if args.full and "pyramid" in timing:
         # one timed region = the image pass of one ingest chunk (the chunk's
         # left images; no stage reads a right pyramid): the level-1 launch and
         # the levels 2-3 tail launch back to back on the context stream
@@ -982,14 +1036,14 @@ def main():
                                                    "bar": 1e-4}
 
     if rank == 0:
-        gn_ev, mp_ev = pmc_evidence(W, H, breakdown, stereo_vo, n_map)
+        gn_ev, mp_ev = pmc_evidence(W, H, breakdown, stereo_vo, n_map) if args.full else (None, None)
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
             "steps": steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / steps, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             "dtype": "f64" if args.precision == "faithful" else "f32 per-pixel, f64 sums and solve",
-            "precision": args.precision,
+            "precision": args.precision, "full": args.full,
             "data": "synthetic" if source == "synthetic" else f"KITTI-format PNG pairs ({source})",
             "units_note": ("a frame = one stereo pair through the reference path (Viso::OnNewFrame on the "
                            "left image); frames are resident in HBM before the clock (no PCIe in value); the "

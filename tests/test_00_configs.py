@@ -363,12 +363,13 @@ def test_gpu_config3_rccl_process_group_one_rank(tmp_path):
     max-over-ranks time by an RCCL all-reduce and gathers the pose log through
     RCCL (viso_amd/shard.py); the gathered log equals the oracle's."""
     dump = str(tmp_path / "poses.npz")
+    outs = tmp_path / "outputs"
     env = dict(os.environ, VISO_DIST_FORCE="1", MASTER_ADDR="127.0.0.1")
     env.pop("VISO_DIST_BACKEND", None)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--dump-poses", dump] + _BENCH_SMALL
+           "--gpus", "1", "--dump-poses", dump, "--dump-outputs", str(outs)] + _BENCH_SMALL
     line = _bench_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=100))
     assert line["n_gpus"] == 1 and line["init_frames_timed"] == 0
     g = line["pose_gather"]
@@ -377,6 +378,18 @@ def test_gpu_config3_rccl_process_group_one_rank(tmp_path):
     d = np.load(dump)
     ov = _oracle_stereo_poses(0, int(d["warm"]) + 20)
     assert _rel_rows(d["rank0"], ov.poses()[int(d["warm"]) - 1:]).max() <= 1e-10
+    # --dump-outputs: what the timed path returned after its last step, as
+    # float64 .npy files; a plain run (no --full) carries no side leg
+    assert line["full"] is False and line["cpu_baseline"] is None and line["roofline"] is None
+    got = {p.name: np.load(p) for p in outs.iterdir()}
+    assert set(got) == {"poses.npy", "points.npy", "align_keyframe.npy", "align_success.npy",
+                        "align_before.npy", "align_after.npy"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["poses.npy"], d["rank0"])
+    assert np.array_equal(got["points.npy"], ov.points())
+    opk, osc, oub, oua = ov.alignment()
+    assert np.array_equal(got["align_keyframe.npy"], opk) and np.array_equal(got["align_success.npy"], osc)
+    assert np.max(np.abs(got["align_after.npy"] - oua)) < 1e-6
 
 
 # ------------------------------------------------------------------ configs[4]

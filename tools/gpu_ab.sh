@@ -17,10 +17,10 @@ b=d['kernels_breakdown_chunk']
 print(f\"{sys.argv[2]:16s} {d['value']:9.1f} frames/s  direct {b['direct']['avg_ms']*1e3:6.2f} us/frame  lk {b['lkalign']['avg_ms']*1e3:7.1f} us/batch  pyr {b['pyramid']['avg_ms']*1e3:6.2f} us\")" $1 $2; }
 for rep in 1 2; do
 for prec in faithful fast; do
-timeout -k 10 200 python -u bench.py --no-cpu --no-svo --rig-steps 0 --precision $prec > $OUT/p_${prec}_$rep.json 2> $OUT/p_${prec}_$rep.err || { tail -20 $OUT/p_${prec}_$rep.err; exit 1; }
+timeout -k 10 200 python -u bench.py --full --no-cpu --no-svo --rig-steps 0 --precision $prec > $OUT/p_${prec}_$rep.json 2> $OUT/p_${prec}_$rep.err || { tail -20 $OUT/p_${prec}_$rep.err; exit 1; }
 summ $OUT/p_${prec}_$rep.json "prod-$prec"
 if [ -n "$V" ]; then
-VISO_LIB=$V timeout -k 10 200 python -u bench.py --no-cpu --no-svo --rig-steps 0 --precision $prec > $OUT/v_${prec}_$rep.json 2> $OUT/v_${prec}_$rep.err || { tail -20 $OUT/v_${prec}_$rep.err; exit 1; }
+VISO_LIB=$V timeout -k 10 200 python -u bench.py --full --no-cpu --no-svo --rig-steps 0 --precision $prec > $OUT/v_${prec}_$rep.json 2> $OUT/v_${prec}_$rep.err || { tail -20 $OUT/v_${prec}_$rep.err; exit 1; }
 summ $OUT/v_${prec}_$rep.json "var-$prec"
 fi
 done

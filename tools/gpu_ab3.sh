@@ -17,9 +17,9 @@ for rep in $(seq ${REPS:-2}); do
 for arg in "$@"; do
   lib=${arg%@*}; ev=""; [ "$arg" != "$lib" ] && ev=${arg#*@}
   n=$(basename $lib .so)${ev:+_${ev//=/}}
-  env $ev VISO_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --gpus 1 --steps 20 --warmup 5 $SMALL > $OUT/${n}_d$rep.json 2> $OUT/${n}_d$rep.err || { tail -20 $OUT/${n}_d$rep.err; exit 1; }
+  env $ev VISO_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 $SMALL > $OUT/${n}_d$rep.json 2> $OUT/${n}_d$rep.err || { tail -20 $OUT/${n}_d$rep.err; exit 1; }
   summ $OUT/${n}_d$rep.json "$n-driver"
-  env $ev VISO_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py $SMALL > $OUT/${n}_f$rep.json 2> $OUT/${n}_f$rep.err || { tail -20 $OUT/${n}_f$rep.err; exit 1; }
+  env $ev VISO_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --full $SMALL > $OUT/${n}_f$rep.json 2> $OUT/${n}_f$rep.err || { tail -20 $OUT/${n}_f$rep.err; exit 1; }
   summ $OUT/${n}_f$rep.json "$n-default"
 done
 done

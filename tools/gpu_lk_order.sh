@@ -16,9 +16,9 @@ print(f\"{sys.argv[2]:22s} {d['value']:9.1f} frames/s  ms/step {d['ms_per_step']
 for rep in 1 2; do
 for lib in prod base; do
   if [ $lib = base ]; then export VISO_LIB=$B; else unset VISO_LIB; fi
-  timeout -k 10 200 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-svo --rig-steps 0 > $OUT/${lib}_d$rep.json 2> $OUT/${lib}_d$rep.err || { tail -20 $OUT/${lib}_d$rep.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-svo --rig-steps 0 > $OUT/${lib}_d$rep.json 2> $OUT/${lib}_d$rep.err || { tail -20 $OUT/${lib}_d$rep.err; exit 1; }
   summ $OUT/${lib}_d$rep.json "$lib-driverargs"
-  timeout -k 10 200 python -u bench.py --no-cpu --no-svo --rig-steps 0 > $OUT/${lib}_f$rep.json 2> $OUT/${lib}_f$rep.err || { tail -20 $OUT/${lib}_f$rep.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --no-cpu --no-svo --rig-steps 0 > $OUT/${lib}_f$rep.json 2> $OUT/${lib}_f$rep.err || { tail -20 $OUT/${lib}_f$rep.err; exit 1; }
   summ $OUT/${lib}_f$rep.json "$lib-default"
 done
 done

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # tag, env...
   local tag=$1; shift
-  env "$@" timeout -k 10 200 python -u bench.py --no-cpu --no-svo --rig-steps 0 > $OUT/$tag.json 2> $OUT/$tag.err || { tail -20 $OUT/$tag.err; return 1; }
+  env "$@" timeout -k 10 200 python -u bench.py --full --no-cpu --no-svo --rig-steps 0 > $OUT/$tag.json 2> $OUT/$tag.err || { tail -20 $OUT/$tag.err; return 1; }
   python -c "
 import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 b=d['kernels_breakdown_chunk'];print(sys.argv[2], d['value'], d['other_precision']['value'], 'direct', round(b['direct']['avg_ms']*1e3,2), 'lk', round(b['lkalign']['avg_ms']*1e3,1), b['lkalign']['launches'])" $OUT/$tag.json $tag

@@ -9,7 +9,7 @@ TAG=${1:-pmc}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python -u bench.py --no-cpu --no-svo --rig-steps 0 --steps 100 --warmup 20"
+B="python -u bench.py --full --no-cpu --no-svo --rig-steps 0 --steps 100 --warmup 20"
 timeout -s KILL 90 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE -d $OUT/gn_occ -o run --output-format csv -- $B > $OUT/gn_occ.log 2>&1 || { echo "gn_occ failed"; tail -20 $OUT/gn_occ.log; exit 1; }
 echo gn_occ ok
 timeout -s KILL 90 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/svo_f -o run --output-format csv -- python -u tools/bench_svo.py > $OUT/svo_f.log 2>&1 || { echo "svo_f failed"; tail -20 $OUT/svo_f.log; exit 1; }

@@ -16,7 +16,7 @@ SRC=$(timeout -k 10 60 python -c "import viso_amd._lib as l; print(l.built_hash(
 SMALL="--no-cpu --no-svo --no-other --rig-steps 0 --no-init --no-config2 --no-host-ingest"
 for cfg in "20 --batch 20 --steps 20 --warmup 5" "64 --steps 128 --warmup 20"; do
   set -- $cfg; n=$1; shift
-  B="python -u bench.py $SMALL $@"
+  B="python -u bench.py --full $SMALL $@"
   timeout -s KILL 90 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pyr_f$n -o run --output-format csv -- $B > $OUT/pyr_f$n.log 2>&1 || { echo "pyr_f$n failed"; tail -20 $OUT/pyr_f$n.log; exit 1; }
   timeout -s KILL 90 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pyr_w$n -o run --output-format csv -- $B > $OUT/pyr_w$n.log 2>&1 || { echo "pyr_w$n failed"; tail -20 $OUT/pyr_w$n.log; exit 1; }
   F=$(find $OUT/pyr_f$n -name '*counter_collection.csv' | head -1); W=$(find $OUT/pyr_w$n -name '*counter_collection.csv' | head -1)
