@@ -315,6 +315,15 @@ public:
         return s;
     }
 
+    // Map growth for the monocular path (viso_set_mono_keyframes: the
+    // triangulation Viso::Reconstruct, src/viso.cpp:434-501, sketches), and
+    // the photometric BA after each insertion (viso_set_bundle_adjust).
+    void SetMonoKeyframes(int interval, int ngood_permille = 500, int cell = 16, double min_parallax_deg = 0.25) {
+        check(viso_set_mono_keyframes(ctx_, interval, ngood_permille, cell, min_parallax_deg),
+              "viso_set_mono_keyframes");
+    }
+    void SetBundleAdjust(int iterations) { check(viso_set_bundle_adjust(ctx_, iterations), "viso_set_bundle_adjust"); }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

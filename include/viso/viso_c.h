@@ -276,6 +276,50 @@ int viso_set_stereo(viso_ctx* ctx, double baseline, int32_t max_disp, int32_t mi
  * reference's frozen map. */
 int viso_set_keyframes(viso_ctx* ctx, int32_t interval, int32_t ngood_permille);
 
+/* Monocular keyframe insertion (the repo's own spec, restated in
+ * tests/mono_kf_ref.py; DESIGN.md §Monocular keyframe insertion): the map of
+ * src/viso.cpp:79-96 grows without a right image, by the two-view
+ * triangulation the reference sketches in Viso::Reconstruct
+ * (src/viso.cpp:434-501) and never calls.  The schedule and the gate are
+ * those of viso_set_keyframes: after every interval-th tracking frame c whose
+ * level-0 nGood is below ngood_permille / 1000 of the map size, with fewer
+ * than 8 keyframes, against the latest keyframe k:
+ *  - the map points that project into c mark their cell of a grid of
+ *    cell x cell pixels; every unmarked cell keeps its FAST corner
+ *    (src/viso.cpp:104, fast_thresh) with the highest score;
+ *  - the winners are tracked into k by OpticalFlowMultiLevel
+ *    (src/viso.cpp:353-391, inverse), seeded by the rotation-only warp
+ *    K R_kc K^-1, R_kc = R_k R_c^T;
+ *  - each track is triangulated (Viso::Triangulate, src/viso.cpp:393-431)
+ *    for the known motion [R_kc | t_k - R_kc t_c] and kept when both depths
+ *    are positive, both reprojection errors (src/viso.cpp:476-497) are within
+ *    projection_error_thresh and the parallax angle at the point is at least
+ *    min_parallax_deg (the reference's disabled block, src/viso.cpp:458-474,
+ *    rejects such points instead).
+ * The kept points are appended in world coordinates (up to 16384 map points),
+ * c becomes a keyframe, viso_set_bundle_adjust's BA runs if it is on, and
+ * stats[14] = points added, stats[15] = keyframes; when no point is kept no
+ * keyframe is made.  Each check is one host synchronisation, an insertion one
+ * more (the count of kept points).  interval 0 (default) = off.
+ * VISO_ERR_ARG unless 8 <= cell <= 64 and 0 <= min_parallax_deg < 90;
+ * VISO_ERR_STATE while viso_set_keyframes is on (and viso_set_keyframes with
+ * interval > 0 returns VISO_ERR_STATE while this is on). */
+int viso_set_mono_keyframes(viso_ctx* ctx, int32_t interval, int32_t ngood_permille, int32_t cell,
+                            double min_parallax_deg);
+/* Stage entry (parity tests): the new points of one such insertion on host
+ * data, by the launches of the frame path.  cur_pyr, kf_pyr: the pyramids of
+ * c and k (as viso_klt takes them); pose_c, pose_k: their Tcw poses; points:
+ * n_points x 3 world (the map; 0..16384).  Outputs: new_points (world; *n =
+ * the number kept, only the first cap written, as viso_fast), winners_xy
+ * (x, y per cell winner in corner order) and accept (1 = kept) for
+ * ceil(width / cell) * ceil(height / cell) entries at most (either may be
+ * NULL), counts = {corners, winners, KLT successes, kept}. */
+int viso_mono_points(viso_ctx* ctx, const uint8_t* cur_pyr, const uint8_t* kf_pyr, int32_t width,
+                     int32_t height, const double pose_c[12], const double pose_k[12],
+                     const double* points, int32_t n_points, int32_t cell, double min_parallax_deg,
+                     double* new_points, int32_t* winners_xy, uint8_t* accept, size_t cap, size_t* n,
+                     int32_t counts[4]);
+
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;
  * oracle/oracle_ba.cpp): after every stereo keyframe insertion, `iterations`
@@ -284,6 +328,10 @@ int viso_set_keyframes(viso_ctx* ctx, int32_t interval, int32_t ngood_permille);
  * keyframe but its host), points marginalised (Schur complement).
  * 0 = off (default). */
 int viso_set_bundle_adjust(viso_ctx* ctx, int32_t iterations);
+/* The map's keyframe poses (Map::keyframes_, include/map.h; Tcw, 12 doubles
+ * each, in insertion order, as the BA last left them): the first
+ * min(cap, keyframes) are written; *n = the keyframe count. */
+int viso_get_keyframe_poses(viso_ctx* ctx, double* Tcw12, size_t cap, size_t* n);
 /* Stage entry (parity tests): the same BA on host data.  kf_images: n_kf
  * (2..8) level-0 images of the context's size; kf_poses: n_kf x 12 (in/out;
  * keyframe 0 fixed); points: n x 3 world (in/out), 1 <= n <= 16384; host: n

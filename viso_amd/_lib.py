@@ -82,6 +82,10 @@ SIGNATURES = {
     "viso_set_stereo": [_vp, _d, _i32, _i32],
     "viso_set_keyframes": [_vp, _i32, _i32],
     "viso_set_bundle_adjust": [_vp, _i32],
+    "viso_get_keyframe_poses": [_vp, _vp, _sz, _vp],
+    "viso_set_mono_keyframes": [_vp, _i32, _i32, _i32, _d],
+    "viso_mono_points": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _d, _vp, _vp, _vp, _sz, _vp,
+                         _vp],
     "viso_photometric_ba": [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
     "viso_version": [],
     # north-star stereo VO (include/viso/viso_svo.h)

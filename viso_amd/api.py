@@ -164,6 +164,32 @@ class Context:
                   max_disp, _p(d), _p(s))
         return d, s
 
+    def mono_points(self, cur_pyr, kf_pyr, width: int, height: int, pose_c, pose_k, points, cell: int = 16,
+                    min_parallax_deg: float = 0.25, cap: int | None = None):
+        """viso_mono_points: the new points of one monocular keyframe
+        insertion (viso_set_mono_keyframes) of frame c against keyframe k.
+        Pyramids as ``pyramid`` returns them, poses 12 doubles (Tcw), points
+        (n, 3) the map.  Returns dict(points (min(kept, cap), 3) world, n kept,
+        xy (winners, 2), accept (winners,), counts [corners, winners, KLT
+        successes, kept])."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        pc = np.ascontiguousarray(pose_c, dtype=np.float64).reshape(12)
+        pk = np.ascontiguousarray(pose_k, dtype=np.float64).reshape(12)
+        cells = -(-width // cell) * -(-height // cell) if cell > 0 else 1
+        cap = cells if cap is None else int(cap)
+        out = np.zeros((max(cap, 1), 3), np.float64)
+        xy = np.zeros((max(cells, 1), 2), np.int32)
+        acc = np.zeros(max(cells, 1), np.uint8)
+        counts = np.zeros(4, np.int32)
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_mono_points", self.h, _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)),
+                  _p(np.ascontiguousarray(kf_pyr, dtype=np.uint8)), width, height, _p(pc), _p(pk), _p(pts),
+                  pts.shape[0], int(cell), float(min_parallax_deg), _p(out), _p(xy), _p(acc), cap,
+                  ctypes.byref(n), _p(counts))
+        nw = int(counts[1])
+        return {"points": out[:min(n.value, cap)].copy(), "n": int(n.value), "xy": xy[:nw].copy(),
+                "accept": acc[:nw].copy(), "counts": [int(c) for c in counts]}
+
     # ------------------------------------------------------------ timing
     def photometric_ba(self, kf_images, kf_poses, points, host, iterations: int = 5):
         """viso_photometric_ba: the BA of include/bundle_adjuster.h:22-106 on
@@ -196,6 +222,13 @@ class Context:
 
     def synchronize(self):
         _lib.call("viso_synchronize", self.h)
+
+
+def mono_points(cur_pyr, kf_pyr, width, height, pose_c, pose_k, points, cell=16, min_parallax_deg=0.25,
+                cap=None, K=None, device: int = 0):
+    """``Context.mono_points`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).mono_points(cur_pyr, kf_pyr, width, height, pose_c, pose_k,
+                                                                points, cell, min_parallax_deg, cap)
 
 
 def default_context(width: int = 640, height: int = 480, device: int = 0, K=None) -> Context:

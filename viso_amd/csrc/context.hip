@@ -410,6 +410,7 @@ extern "C" int viso_set_stereo(viso_ctx* c, double baseline, int32_t max_disp, i
 
 extern "C" int viso_set_keyframes(viso_ctx* c, int32_t interval, int32_t ngood_permille) {
     if (!c || interval < 0 || ngood_permille < 0 || ngood_permille > 1000) return VISO_ERR_ARG;
+    if (interval > 0 && c->mkf_interval > 0) return VISO_ERR_STATE;  // one insertion mode at a time
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     c->kf_interval = interval;
     c->kf_permille = ngood_permille;
@@ -420,6 +421,17 @@ extern "C" int viso_set_bundle_adjust(viso_ctx* c, int32_t iterations) {
     if (!c || iterations < 0 || iterations > 100) return VISO_ERR_ARG;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     c->ba_iterations = iterations;
+    return VISO_OK;
+}
+
+extern "C" int viso_get_keyframe_poses(viso_ctx* c, double* Tcw12, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    const size_t m = std::min(cap, c->kf_slots.size());
+    if (m > 0 && Tcw12) VISO_HIP_CHECK(hipMemcpyAsync(Tcw12, c->kf_poses.ptr, 96 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (n) *n = c->kf_slots.size();
     return VISO_OK;
 }
 

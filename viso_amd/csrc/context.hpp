@@ -330,6 +330,21 @@ struct viso_ctx {
     int bundle_adjust();
     int stereo_points_into(int cur, double* out, int cap, int* kept);
     int insert_keyframe(int cur);
+    // the m camera-frame points appended behind the map -> world, cur becomes
+    // a keyframe, BA, LK templates (the tail of every insertion)
+    int append_keyframe(int cur, int m);
+    // monocular keyframe insertion (viso_set_mono_keyframes; monokf.hip): the
+    // schedule and gate of kf_interval / kf_permille without a right image;
+    // new points by triangulation against the latest keyframe, one corner per
+    // unoccupied mkf_cell-pixel cell.  Exclusive with kf_interval > 0.
+    int mkf_interval = 0, mkf_permille = 0, mkf_cell = 16;
+    double mkf_parallax_deg = 0.0;
+    viso::DevBuf mono_buf;
+    bool kf_on() const { return kf_interval > 0 || mkf_interval > 0; }
+    int mono_launch(viso::MonoKfArgs& a, const viso::FrameDev& fc, const viso::FrameDev& fk, const viso::PyrGeom& g,
+                    viso::FastScratch& fs, const double* pose_c, const double* pose_k, const double* points,
+                    int n_points, int cell, double min_parallax_deg, double* out, int out_cap);
+    int insert_mono_keyframe(int cur);
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

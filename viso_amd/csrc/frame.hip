@@ -228,7 +228,7 @@ void viso_ctx::release() {
                       &kp1, &kp2, &kp1b, &kp2b, &track_success, &n_track_dev, &fast_rows,
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
-                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf};
+                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -648,7 +648,7 @@ int viso_ctx::host_lk_batch() const {
 int viso_ctx::finish_host_call() {
     // outside tracking, and with keyframe insertion (its decision reads the
     // frame's nGood at once), as every other call
-    if (state != VISO_STATE_RUNNING || kf_interval > 0 || bg_active) return finish_call(lk_stream);
+    if (state != VISO_STATE_RUNNING || kf_on() || bg_active) return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
     if ((int)lk_pending.size() > host_lk_batch()) return flush_lk_frames(lk_stream, true);
@@ -679,7 +679,7 @@ bool viso_ctx::host_queue_eligible() {
         const char* e = getenv("VISO_HOST_CHUNK");
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
-    return host_chunk > 0 && state == VISO_STATE_RUNNING && kf_interval <= 0 && bg_on() &&
+    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && bg_on() &&
            direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
@@ -801,7 +801,7 @@ int viso_ctx::stage_poses() {
 // frame of such a chunk is a tracking frame, so every ready flag is raised:
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
-                                      lk_tmpl.ptr && kf_interval <= 0 && !dpend && lk_pending.empty(); }
+                                      lk_tmpl.ptr && !kf_on() && !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1100,10 +1100,16 @@ int viso_ctx::insert_keyframe(int cur) {
     int rc = stereo_points_into(cur, (double*)map_pts.ptr + 3 * (size_t)n_map, cap, &m);
     stats[1] = saved1;
     if (rc) return rc;
+    return append_keyframe(cur, m);
+}
+
+// The tail of an insertion, stereo or monocular: the m new points behind the
+// map are in cur's camera frame.
+int viso_ctx::append_keyframe(int cur, int m) {
     launch_points_to_world((double*)map_pts.ptr + 3 * (size_t)n_map, m, pose_of(cur), stream);
     VISO_HIP_CHECK(hipGetLastError());
     n_map += m;
-    rc = own_level0(cur);
+    int rc = own_level0(cur);
     if (rc) return rc;
     kf_slots.push_back(cur);
     hold(cur);
@@ -1407,19 +1413,22 @@ int viso_ctx::on_new_frame(int cur) {
                 }
             }
             ran_tracking = true;
-            // stereo keyframe insertion (oracle_viso.cpp): every
-            // kf_interval-th tracking frame, one host sync for its nGood
+            // keyframe insertion (stereo: oracle_viso.cpp; monocular:
+            // monokf.hip): every interval-th tracking frame, one host sync
+            // for its nGood
             ++track_cnt;
             stats[15] = (double)kf_slots.size();  // before a possible insertion, as the oracle
-            if (kf_interval > 0 && right_l0 && stereo_base > 0 && track_cnt % kf_interval == 0 &&
-                (int)kf_slots.size() < kMaxKeyframes) {
+            const bool mono_kf = mkf_interval > 0;
+            const int interval = mono_kf ? mkf_interval : (right_l0 && stereo_base > 0) ? kf_interval : 0;
+            const int permille = mono_kf ? mkf_permille : kf_permille;
+            if (interval > 0 && track_cnt % interval == 0 && (int)kf_slots.size() < kMaxKeyframes) {
                 int rc = finish_call(stream);
                 if (rc) return rc;
                 VISO_HIP_CHECK(hipMemcpyAsync(h_dbl, direct_stats.ptr, sizeof(double), hipMemcpyDeviceToHost,
                                               stream));
                 VISO_HIP_CHECK(hipStreamSynchronize(stream));
-                if (h_dbl[0] < kf_permille * (double)n_map / 1000.0) {
-                    rc = insert_keyframe(cur);
+                if (h_dbl[0] < permille * (double)n_map / 1000.0) {
+                    rc = mono_kf ? insert_mono_keyframe(cur) : insert_keyframe(cur);
                     if (rc) return rc;
                     stats[15] = (double)kf_slots.size();
                 }

@@ -163,6 +163,47 @@ void launch_stereo_sad(const uint8_t* left, const uint8_t* right, int w, int h, 
                        const int* ys, int n, int max_disp, int* disp, int* sad,
                        hipStream_t stream);
 
+// ---------------------------------------------------------------- monocular keyframe insertion
+// One insertion of viso_set_mono_keyframes (monokf.hip): the current frame c
+// against the latest keyframe k.  Poses and points in device memory; the
+// scratch members are carved from mono_kf_scratch_bytes() bytes by
+// mono_kf_scratch_at (cap_win = the grid's cells: a cell has one winner).
+struct MonoKfArgs {
+    int w, h, cell, ncx, ncy;
+    double K[4];  // fx, fy, cx, cy
+    double Kinv[9];
+    double proj_thresh;     // pixels
+    double cos_thresh;      // cos(min_parallax_deg)
+    const double* pose_c;   // 12, Tcw
+    const double* pose_k;
+    const double* map_pts;  // n_map x 3 (world)
+    int n_map;
+    const int4* corners;    // FAST's {x, y, score, 0}, row-major
+    const int* n_corners;   // FAST's count (uncapped)
+    int cap_corners;
+    unsigned long long* cell_key;  // [ncy][ncx]: marked, or the best (score, first index)
+    float2* kp1;                   // winners (c), KLT seed / result (k)
+    float2* kp2;
+    int2* win_xy;
+    uint8_t* success;  // KLT's
+    uint8_t* accept;
+    int* wave_cnt;     // accepted per wave of the triangulation grid
+    double* cand_pts;  // cap_win x 3 (c's camera frame)
+    int cap_win;
+    int* counts;  // {corners, winners, KLT successes, accepted}
+    double* out;  // accepted points in candidate order (c's camera frame)
+    int out_cap;
+};
+int mono_kf_cells(int w, int h, int cell);
+size_t mono_kf_scratch_bytes(int w, int h, int cell, int cap_corners);
+size_t mono_kf_scratch_at(MonoKfArgs& a, void* base, int w, int h, int cell, int cap_corners);
+// the map's occupancy of c, the cell winners of a.corners compacted in
+// corner order into kp1 / win_xy with the KLT seed in kp2; counts[0..1]
+void launch_mono_candidates(const MonoKfArgs& a, hipStream_t stream);
+// behind the KLT (kp2, success): triangulation, filter, ordered compaction
+// of the accepted points into out; counts[2..3]
+void launch_mono_triangulate(const MonoKfArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

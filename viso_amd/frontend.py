@@ -114,6 +114,17 @@ class Viso(FrameHandler):
         poses and map points (0 = off)."""
         _lib.call("viso_set_bundle_adjust", self.ctx.h, int(iterations))
 
+    def set_mono_keyframes(self, interval: int, ngood_permille: int = 500, cell: int = 16,
+                           min_parallax_deg: float = 0.25) -> None:
+        """Monocular keyframe insertion (viso_set_mono_keyframes): the schedule
+        and gate of set_keyframes without a right image; the frame's best FAST
+        corner of every `cell`-pixel cell no map point projects into is tracked
+        into the latest keyframe, triangulated for the known motion and kept
+        when it reprojects within projection_error_thresh with at least
+        `min_parallax_deg` of parallax.  interval 0 = off."""
+        _lib.call("viso_set_mono_keyframes", self.ctx.h, int(interval), int(ngood_permille), int(cell),
+                  float(min_parallax_deg))
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
@@ -151,6 +162,15 @@ class Viso(FrameHandler):
         out = np.zeros((n.value, 4), np.float64)
         if n.value:
             _lib.call("viso_get_frame_log", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
+        return out
+
+    def keyframe_poses(self) -> np.ndarray:
+        """The map's keyframe poses (viso_get_keyframe_poses): (keyframes, 12) Tcw."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_keyframe_poses", self.ctx.h, None, 0, ctypes.byref(n))
+        out = np.zeros((n.value, 12), np.float64)
+        if n.value:
+            _lib.call("viso_get_keyframe_poses", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
         return out
 
     def tracks(self):
