@@ -159,6 +159,22 @@ def direct_pose(last_pyr, cur_pyr, w, h, K, points, pose_last, pose_init):
     return pio
 
 
+def direct_pose_level(last_pyr, cur_pyr, w, h, K, points, pose_last, pose_in, level):
+    """One pyramid level of the direct pose (oracle_direct_pose_level): returns
+    (pose12 after the level, stats[50] of its last iteration: nGood, cost,
+    H (36, row-major), b (6), update (6))."""
+    lib = load()
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    Kd = np.asarray(K, np.float64)
+    pl = np.ascontiguousarray(pose_last, np.float64).reshape(12)
+    pio = np.ascontiguousarray(pose_in, np.float64).reshape(12).copy()
+    stats = np.zeros(50)
+    lib.oracle_direct_pose_level(ptr(np.ascontiguousarray(last_pyr)), ptr(np.ascontiguousarray(cur_pyr)),
+                                 w, h, ptr(Kd), ptr(pts), pts.shape[0], ptr(pl), ptr(pio), int(level),
+                                 ptr(stats))
+    return pio, stats
+
+
 def lk_align(kf_pyrs, kf_poses, cur_pyr, cur_pose, w, h, K, points, thresh=14400.0):
     lib = load()
     kfs = [np.ascontiguousarray(k, np.uint8) for k in kf_pyrs]

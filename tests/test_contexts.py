@@ -13,6 +13,8 @@ log's pinned staging past its first 4,096 entries.
 * viso_get_poses past 4,096 poses: the pinned staging grows
   geometrically and the kernels keep mirroring new poses into it; poses read
   after every call equal the log read once at the end by a second context.
+  A partial read (4096 < cap < n_poses) that triggers the growth must still
+  stage every logged pose: a later full read equals the second context's.
 """
 from __future__ import annotations
 
@@ -168,5 +170,62 @@ def test_gpu_pose_log_past_4096():
     for p in reads:
         assert np.array_equal(p.view(np.uint64), ref[:len(p)].view(np.uint64))
     assert len(reads[-1]) == len(ref)
+    a.close()
+    b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_pose_log_partial_read_regrows_staging():
+    """A partial viso_get_poses (4096 < cap < n_poses) is the first read past
+    4,096 poses: the pinned staging regrows while poses cap..n_poses exist in
+    the device log only.  The synchronize after it counts every pose below
+    the new capacity as staged, so the regrow has to bring all of them over,
+    not just the `cap` rows it returns.  33 unread cycles (4,162 poses), a
+    read of 4,100, synchronize, one more cycle, synchronize, then a full read
+    equals, bit for bit, the log a second context reads once at the end."""
+    import ctypes
+
+    import torch
+
+    import viso_amd
+    from viso_amd import _lib
+    d = _frames(0)
+    seq = d["seq"]
+    fwd = list(range(WARM, WARM + 64))
+    cyc = fwd + fwd[-2:0:-1]
+    left = np.stack([seq.image(f, 0) for f in range(max(cyc) + 1)])
+    frames = torch.from_numpy(np.ascontiguousarray(left[cyc])).cuda()
+    dl0, dr0 = torch.from_numpy(d["left"][:WARM]).cuda(), torch.from_numpy(d["right"]).cuda()
+    torch.cuda.synchronize()
+    reps, cap = 33, 4100
+
+    def make():
+        v = viso_amd.Viso(*seq.K, width=W, height=H, enable_tracking=1, batch_frames=128, max_poses=8192)
+        v.set_stereo(seq.p.baseline, STEREO_MAX_DISP, 1)
+        v.process_device(dl0.data_ptr(), dr0.data_ptr(), WARM, W * H)
+        v.synchronize()
+        assert v.state == 1
+        return v
+
+    a, b = make(), make()
+    for _ in range(reps):
+        for v in (a, b):
+            v.process_device(frames.data_ptr(), None, len(cyc), W * H)
+    n = ctypes.c_size_t(0)
+    part = np.zeros((cap, 12), np.float64)
+    _lib.call("viso_get_poses", a.ctx.h, part.ctypes.data, cap, ctypes.byref(n))
+    assert 4096 < cap < n.value == WARM - 1 + reps * len(cyc)
+    a.synchronize()
+    for v in (a, b):
+        v.process_device(frames.data_ptr(), None, len(cyc), W * H)
+    a.synchronize()
+    got = a.poses
+    b.synchronize()
+    ref = b.poses
+    assert len(ref) == WARM - 1 + (reps + 1) * len(cyc)
+    assert got.shape == ref.shape
+    assert np.array_equal(part.view(np.uint64), ref[:cap].view(np.uint64))
+    bad = np.flatnonzero((got.view(np.uint64) != ref.view(np.uint64)).any(axis=1))
+    assert bad.size == 0, f"{bad.size} poses differ, rows {bad[0]}..{bad[-1]}"
     a.close()
     b.close()

@@ -714,8 +714,15 @@ __device__ inline bool direct_point_fast(const DirectArgs& a, const LevelPair& f
         t32 = tap_f32(C, n, o + 2 * w + 1);
     }
     const float i0 = bilerp_f32(t11, t12, t21, t22, xx, yy);
-    const float g0 = 0.5f * (bilerp_f32(t12, t13, t22, t23, xx, yy) - bilerp_f32(t10, t11, t20, t21, xx, yy));
-    const float g1 = 0.5f * (bilerp_f32(t21, t22, t31, t32, xx, yy) - bilerp_f32(t01, t02, t11, t12, xx, yy));
+    // A gradient sample at a coordinate in (-1, 0) (the patch's first column
+    // or row for a projection in [4, 5)): sample_px truncates it to base 0
+    // ((int)x, the reference's rule), not floor's -1, and keeps the fraction,
+    // so it reads the centre sample's taps with the centre sample's weights
+    const bool trunc_x = ix == 0 && uc > fu, trunc_y = iy == 0 && vc > fv;
+    const float left = trunc_x ? i0 : bilerp_f32(t10, t11, t20, t21, xx, yy);
+    const float up = trunc_y ? i0 : bilerp_f32(t01, t02, t11, t12, xx, yy);
+    const float g0 = 0.5f * (bilerp_f32(t12, t13, t22, t23, xx, yy) - left);
+    const float g1 = 0.5f * (bilerp_f32(t21, t22, t31, t32, xx, yy) - up);
     const float error = lval - i0;
     float J[6];
 #pragma unroll

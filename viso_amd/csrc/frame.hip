@@ -1644,6 +1644,7 @@ int viso_get_poses(viso_ctx* c, double* Tcw12, size_t cap, size_t* n) {
         std::memcpy(Tcw12, c->h_poses, 96 * m);
         return VISO_OK;
     }
+    size_t rows = m;
     if (c->h_poses_cap < m) {
         // geometric growth (up to max_poses): the kernels then mirror the
         // poses logged after this call into the new buffer (log_host), and
@@ -1660,10 +1661,15 @@ int viso_get_poses(viso_ctx* c, double* Tcw12, size_t cap, size_t* n) {
         VISO_HIP_CHECK(hipHostMalloc((void**)&c->h_poses, 96 * want));
         VISO_HIP_CHECK(hipHostGetDevicePointer((void**)&c->h_poses_dev, c->h_poses, 0));
         c->h_poses_cap = want;
+        // the new buffer holds nothing yet, and stage_poses counts every pose
+        // below its capacity as mirrored by the kernels: a partial read
+        // (cap < n_poses) must still bring over all logged poses that fit,
+        // not only the m it returns
+        rows = std::min(want, std::min((size_t)c->n_poses, (size_t)std::max(c->p.max_poses, 0)));
     }
-    VISO_HIP_CHECK(hipMemcpyAsync(c->h_poses, c->pose_log.ptr, 96 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(c->h_poses, c->pose_log.ptr, 96 * rows, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->poses_staged = std::max(c->poses_staged, m);
+    c->poses_staged = std::max(c->poses_staged, rows);
     std::memcpy(Tcw12, c->h_poses, 96 * m);
     return VISO_OK;
 }
