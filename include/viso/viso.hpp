@@ -324,6 +324,25 @@ public:
     }
     void SetBundleAdjust(int iterations) { check(viso_set_bundle_adjust(ctx_, iterations), "viso_set_bundle_adjust"); }
 
+    // Sliding-window map (viso_set_map_window): at most `window` keyframes;
+    // an insertion into a full window first retires the oldest keyframe and
+    // culls the points it hosts.  0 = off.
+    void SetMapWindow(int window, int cell = 16) { check(viso_set_map_window(ctx_, window, cell), "viso_set_map_window"); }
+    // viso_get_map_window's info[8]
+    std::array<int64_t, 8> MapWindow() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_map_window(ctx_, info.data()), "viso_get_map_window");
+        return info;
+    }
+    // every map point's host keyframe index
+    std::vector<int32_t> GetPointHosts() const {
+        size_t n = 0;
+        check(viso_get_point_hosts(ctx_, nullptr, 0, &n), "viso_get_point_hosts");
+        std::vector<int32_t> out(n);
+        if (n) check(viso_get_point_hosts(ctx_, out.data(), n, &n), "viso_get_point_hosts");
+        return out;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

@@ -183,7 +183,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_LKALIGN 6
 #define VISO_KERNEL_STEREO 7
 #define VISO_KERNEL_UPLOAD 8 /* host -> device copy of a frame (viso_process_frame / _stereo) */
-#define VISO_KERNEL_COUNT 9
+#define VISO_KERNEL_MAPWIN 9 /* one retirement of the sliding-window map (viso_set_map_window) */
+#define VISO_KERNEL_COUNT 10
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -319,6 +320,50 @@ int viso_mono_points(viso_ctx* ctx, const uint8_t* cur_pyr, const uint8_t* kf_py
                      const double* points, int32_t n_points, int32_t cell, double min_parallax_deg,
                      double* new_points, int32_t* winners_xy, uint8_t* accept, size_t cap, size_t* n,
                      int32_t counts[4]);
+
+/* Sliding-window map (the repo's own spec, restated in
+ * tests/map_window_ref.py; DESIGN.md §Sliding-window map): the map follows the
+ * camera instead of filling up.  With window > 0, an insertion check (stereo
+ * or monocular, their schedule and gate) is made while the map holds at most
+ * `window` keyframes; one that passes its gate with exactly `window` of them
+ * first retires the oldest keyframe (index 0), with c the check frame:
+ *  - a pose "sees" a point P when Pc = R P + t has Pc.z > 0 and its
+ *    projection (u, v) lies in [0, width) x [0, height); P's cell in c is
+ *    (int(u / cell), int(v / cell));
+ *  - points hosted by another keyframe stay (host - 1) and, where c sees
+ *    them, mark their cell;
+ *  - a point hosted by the retired keyframe is a candidate when c sees it in
+ *    an unmarked cell and at least one remaining keyframe sees it; of a
+ *    cell's candidates the one with the highest index survives, hosted by the
+ *    newest remaining keyframe that sees it; every other such point is culled;
+ *  - kept points keep their order, the keyframe poses move down one index.
+ * If nothing would be kept the retirement is abandoned and that check inserts
+ * nothing.  Otherwise the check's insertion follows against the culled map.
+ * A retirement is one more host synchronisation.  window 0 (default) = off:
+ * at most 8 keyframes, nothing leaves the map.  VISO_ERR_ARG unless
+ * window == 0, or 2 <= window <= 8 and 8 <= cell <= 64; VISO_ERR_STATE when
+ * the map already holds more than `window` keyframes. */
+int viso_set_map_window(viso_ctx* ctx, int32_t window, int32_t cell);
+/* info = {window, cell, keyframes retired, points culled, and of the last
+ * retirement: the number of frames processed before its check frame (-1: no
+ * retirement yet), the points its keyframe hosted, the survivors among them,
+ * the map size after it}. */
+int viso_get_map_window(viso_ctx* ctx, int64_t info[8]);
+/* Every map point's host keyframe (an index into viso_get_keyframe_poses; the
+ * array the BA is given): the first min(cap, points) are written; *n = the
+ * point count. */
+int viso_get_point_hosts(viso_ctx* ctx, int32_t* host, size_t cap, size_t* n);
+/* Stage entry (parity tests): one retirement on host data, by the launches of
+ * the frame path.  pose_c: the check frame's Tcw; kf_poses: n_kf x 12
+ * (1..8), keyframe 0 the one retired; points: n x 3 world (0..16384); host: n
+ * indices in [0, n_kf).  Outputs: keep (n flags), out_points / out_host (the
+ * kept points in order with their new hosts; room for n), *n_out = the number
+ * kept, counts = {hosted by keyframe 0, of those seen by c, candidates,
+ * survivors}.  VISO_ERR_ARG on any out-of-range argument. */
+int viso_map_retire(viso_ctx* ctx, int32_t width, int32_t height, const double pose_c[12],
+                    const double* kf_poses, int32_t n_kf, const double* points, const int32_t* host,
+                    int32_t n, int32_t cell, double* out_points, int32_t* out_host, uint8_t* keep,
+                    size_t* n_out, int32_t counts[4]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

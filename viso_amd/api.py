@@ -190,6 +190,30 @@ class Context:
         return {"points": out[:min(n.value, cap)].copy(), "n": int(n.value), "xy": xy[:nw].copy(),
                 "accept": acc[:nw].copy(), "counts": [int(c) for c in counts]}
 
+    def map_retire(self, width: int, height: int, pose_c, kf_poses, points, host, cell: int = 16):
+        """viso_map_retire: one retirement of the sliding-window map
+        (viso_set_map_window) on host data: keyframe 0 of kf_poses (k, 12)
+        leaves, c is the check frame.  points (n, 3) world, host (n,) keyframe
+        indices.  Returns dict(points (kept, 3), host (kept,), keep (n,), n
+        kept, counts [retired-host, of those seen by c, candidates,
+        survivors])."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        hst = np.ascontiguousarray(host, dtype=np.int32).reshape(-1)
+        pc = np.ascontiguousarray(pose_c, dtype=np.float64).reshape(12)
+        kp = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        n = pts.shape[0]
+        if hst.shape[0] != n:
+            raise ValueError("map_retire: one host per point")
+        out = np.zeros((max(n, 1), 3), np.float64)
+        oh = np.zeros(max(n, 1), np.int32)
+        keep = np.zeros(max(n, 1), np.uint8)
+        counts = np.zeros(4, np.int32)
+        m = ctypes.c_size_t(0)
+        _lib.call("viso_map_retire", self.h, width, height, _p(pc), _p(kp), kp.shape[0], _p(pts), _p(hst), n,
+                  int(cell), _p(out), _p(oh), _p(keep), ctypes.byref(m), _p(counts))
+        return {"points": out[:m.value].copy(), "host": oh[:m.value].copy(), "keep": keep[:n].copy(),
+                "n": int(m.value), "counts": [int(c) for c in counts]}
+
     # ------------------------------------------------------------ timing
     def photometric_ba(self, kf_images, kf_poses, points, host, iterations: int = 5):
         """viso_photometric_ba: the BA of include/bundle_adjuster.h:22-106 on
@@ -229,6 +253,11 @@ def mono_points(cur_pyr, kf_pyr, width, height, pose_c, pose_k, points, cell=16,
     """``Context.mono_points`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).mono_points(cur_pyr, kf_pyr, width, height, pose_c, pose_k,
                                                                 points, cell, min_parallax_deg, cap)
+
+
+def map_retire(width, height, pose_c, kf_poses, points, host, cell=16, K=None, device: int = 0):
+    """``Context.map_retire`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).map_retire(width, height, pose_c, kf_poses, points, host, cell)
 
 
 def default_context(width: int = 640, height: int = 480, device: int = 0, K=None) -> Context:

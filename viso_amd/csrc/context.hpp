@@ -345,6 +345,18 @@ struct viso_ctx {
                     viso::FastScratch& fs, const double* pose_c, const double* pose_k, const double* points,
                     int n_points, int cell, double min_parallax_deg, double* out, int out_cap);
     int insert_mono_keyframe(int cur);
+    // sliding-window map (viso_set_map_window; mapwin.hip): with win_size
+    // keyframes in the map, an insertion check that passes its gate first
+    // retires keyframe 0 and culls the points it hosts (one survivor per
+    // win_cell-pixel cell of the check frame no live point projects into).
+    // 0 = off.  win_last: {frames at the last retirement (-1: none), its
+    // retired-host points, its survivors, the map size after it}
+    int win_size = 0, win_cell = 16;
+    int64_t win_retired = 0, win_culled = 0;
+    int64_t win_last[4] = {-1, 0, 0, 0};
+    viso::DevBuf mapwin_buf;
+    // *retired = false: nothing would be kept, map and keyframes unchanged
+    int retire_keyframe(int cur, bool* retired);
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

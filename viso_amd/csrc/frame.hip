@@ -228,7 +228,7 @@ void viso_ctx::release() {
                       &kp1, &kp2, &kp1b, &kp2b, &track_success, &n_track_dev, &fast_rows,
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
-                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf};
+                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -1421,15 +1421,32 @@ int viso_ctx::on_new_frame(int cur) {
             const bool mono_kf = mkf_interval > 0;
             const int interval = mono_kf ? mkf_interval : (right_l0 && stereo_base > 0) ? kf_interval : 0;
             const int permille = mono_kf ? mkf_permille : kf_permille;
-            if (interval > 0 && track_cnt % interval == 0 && (int)kf_slots.size() < kMaxKeyframes) {
+            // (sliding-window map, viso_set_map_window: a full window still
+            // checks; the insertion then follows the oldest keyframe's
+            // retirement, mapwin.hip)
+            const int n_kf = (int)kf_slots.size();
+            const bool room = win_size > 0 ? n_kf <= win_size : n_kf < kMaxKeyframes;
+            if (interval > 0 && track_cnt % interval == 0 && room) {
                 int rc = finish_call(stream);
                 if (rc) return rc;
                 VISO_HIP_CHECK(hipMemcpyAsync(h_dbl, direct_stats.ptr, sizeof(double), hipMemcpyDeviceToHost,
                                               stream));
                 VISO_HIP_CHECK(hipStreamSynchronize(stream));
                 if (h_dbl[0] < permille * (double)n_map / 1000.0) {
+                    bool retired = false;
+                    if (win_size > 0 && n_kf == win_size) {
+                        rc = retire_keyframe(cur, &retired);
+                        if (rc) return rc;
+                        if (!retired) break;  // nothing would be kept: no retirement, no insertion
+                    }
                     rc = mono_kf ? insert_mono_keyframe(cur) : insert_keyframe(cur);
                     if (rc) return rc;
+                    // an insertion that made no keyframe left the culled
+                    // map's LK templates to the retirement
+                    if (retired && (int)kf_slots.size() == n_kf - 1) {
+                        rc = build_lk_templates();
+                        if (rc) return rc;
+                    }
                     stats[15] = (double)kf_slots.size();
                 }
             }

@@ -204,6 +204,36 @@ void launch_mono_candidates(const MonoKfArgs& a, hipStream_t stream);
 // of the accepted points into out; counts[2..3]
 void launch_mono_triangulate(const MonoKfArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- sliding-window map
+// One retirement of viso_set_map_window (mapwin.hip): keyframe 0 leaves, the
+// check frame is c.  Poses, points and hosts in device memory; the scratch
+// members are carved from map_window_scratch_bytes() bytes by
+// map_window_scratch_at (cap_points: the most points a launch is given).
+struct MapWinArgs {
+    int w, h, cell, ncx, ncy;
+    double K[4];            // fx, fy, cx, cy
+    const double* pose_c;   // 12, Tcw
+    double* kf_poses;       // n_kf x 12; row k + 1 -> row k when shift_poses and a point is kept
+    int n_kf;
+    int shift_poses;
+    const double* pts;      // n x 3 (world)
+    const int* host;        // n host keyframe indices
+    int n;
+    int* counts;            // {retired-host, of those seen by c, candidates, survivors, kept}
+    int* cell_mark;         // [ncy][ncx]: 1 = a live point projects into it
+    size_t zero_bytes;      // counts and cell_mark, cleared together
+    int* cell_win;          // [ncy][ncx]: the highest candidate index (-1: none)
+    int* pt_cell;           // n: the point's cell in c (-1: c does not see it)
+    int* new_host;          // n: host - 1, a candidate's newest seeing keyframe - 1, or -1
+    uint8_t* keep;          // n
+    int* out_host;          // kept points' hosts and coordinates, in index order
+    double* out_pts;
+};
+size_t map_window_scratch_bytes(int w, int h, int cell, int cap_points);
+size_t map_window_scratch_at(MapWinArgs& a, void* base, int w, int h, int cell, int cap_points);
+// marks, claims, keep flags, the stable compaction and the counts
+void launch_map_retire(const MapWinArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

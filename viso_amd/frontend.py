@@ -125,6 +125,32 @@ class Viso(FrameHandler):
         _lib.call("viso_set_mono_keyframes", self.ctx.h, int(interval), int(ngood_permille), int(cell),
                   float(min_parallax_deg))
 
+    def set_map_window(self, window: int, cell: int = 16) -> None:
+        """Sliding-window map (viso_set_map_window): the map holds at most
+        `window` keyframes (2..8); an insertion into a full window first
+        retires the oldest keyframe and culls the points it hosts, keeping
+        one per `cell`-pixel cell of the frame that no other point projects
+        into and that a remaining keyframe still sees.  window 0 = off."""
+        _lib.call("viso_set_map_window", self.ctx.h, int(window), int(cell))
+
+    def map_window(self) -> np.ndarray:
+        """viso_get_map_window: int64[8] = window, cell, keyframes retired,
+        points culled, then of the last retirement: frames processed before
+        its check frame (-1: none yet), retired-host points, survivors, the
+        map size after it."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_map_window", self.ctx.h, info.ctypes.data)
+        return info
+
+    def point_hosts(self) -> np.ndarray:
+        """Every map point's host keyframe index (viso_get_point_hosts)."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_point_hosts", self.ctx.h, None, 0, ctypes.byref(n))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            _lib.call("viso_get_point_hosts", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
+        return out
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
