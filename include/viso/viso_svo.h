@@ -133,7 +133,8 @@ int viso_svo_match(viso_svo* s, const int32_t* const* u4, const int32_t* const* 
 
 /* Bucketing + RANSAC + Gauss-Newton on matches given as {u_l1, v_l1, u_r1,
  * v_r1, u_l2, v_l2, u_r2, v_r2} (already bucketed).  frame selects the
- * sampler stream.  Output: motion (12), inlier flags, *n_inliers. */
+ * sampler stream.  Output: motion (12), inlier flags, *n_inliers (>= 6), or
+ * on a failed estimate the identity, all flags 0 and *n_inliers = -1. */
 int viso_svo_estimate(viso_svo* s, const int32_t* uv8, int32_t n, int64_t frame, double* motion12,
                       uint8_t* inlier, int32_t* n_inliers);
 

@@ -22,6 +22,7 @@
 
 #include "../include/viso/viso_svo.h"
 #include "oracle_common.hpp"
+#include "viso_oracle.h"
 
 namespace {
 
@@ -403,6 +404,16 @@ bool is_inlier(const double* R, const double* t, const Obs& o, const viso_svo_pa
 
 const double kI3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
+// Which way the last estimate() call ended (oracle_svo_estimate_trace; tests
+// only, per calling thread).  Written beside the result, never read back.
+struct EstimateTrace {
+    int exit_code = ORACLE_SVO_EXIT_FEW_MATCHES;
+    int best_h = -1, best_cnt = -1;  // the winning hypothesis and its inlier count
+    int best_shared = 0;             // another hypothesis reached best_cnt
+    int n_final = -1;                // inliers of the refined motion (-1: not reached)
+};
+thread_local EstimateTrace g_trace;
+
 // the 3 distinct sample indices of hypothesis h (false if 16 draws do not give 3)
 bool sample3(uint64_t seed, int h, int M, int* idx) {
     int got = 0;
@@ -421,6 +432,7 @@ int estimate(const int32_t* uv8, int M, int64_t frame, const viso_svo_params& p,
              uint8_t* inlier, const int32_t* cams = nullptr, const double* extr = nullptr) {
     for (int i = 0; i < 12; ++i) motion[i] = (i < 9) ? kI3[i] : 0.0;
     for (int i = 0; i < M; ++i) inlier[i] = 0;
+    g_trace = EstimateTrace();
     if (M < 6) return -1;
     std::vector<Obs> obs((size_t)M);
     for (int i = 0; i < M; ++i)
@@ -446,24 +458,34 @@ int estimate(const int32_t* uv8, int M, int64_t frame, const viso_svo_params& p,
             best_h = h;
             std::memcpy(bR, R, sizeof(bR));
             std::memcpy(bt, t, sizeof(bt));
+            g_trace.best_shared = 0;
+        } else if (cnt == best_cnt) {
+            g_trace.best_shared = 1;
         }
     }
+    g_trace.best_h = best_h;
+    g_trace.best_cnt = best_cnt;
+    g_trace.exit_code = ORACLE_SVO_EXIT_NO_HYPOTHESIS;
     if (best_h < 0 || best_cnt < 6) return -1;
     for (int i = 0; i < M; ++i) sel[(size_t)i] = is_inlier(bR, bt, obs[(size_t)i], p) ? 1 : 0;
     double R[9], t[3];
     std::memcpy(R, bR, sizeof(R));
     std::memcpy(t, bt, sizeof(t));
+    g_trace.exit_code = ORACLE_SVO_EXIT_OK;
     if (!gauss_newton(obs, sel, p, R, t)) {  // keep the best hypothesis
         std::memcpy(R, bR, sizeof(R));
         std::memcpy(t, bt, sizeof(t));
+        g_trace.exit_code = ORACLE_SVO_EXIT_REFINE_FAILED;
     }
     int n_inl = 0;
     for (int i = 0; i < M; ++i) {
         inlier[i] = is_inlier(R, t, obs[(size_t)i], p) ? 1 : 0;
         n_inl += inlier[i];
     }
+    g_trace.n_final = n_inl;
     if (n_inl < 6) {
         for (int i = 0; i < M; ++i) inlier[i] = 0;
+        g_trace.exit_code = ORACLE_SVO_EXIT_FINAL_FEW;
         return -1;  // motion stays the identity
     }
     for (int i = 0; i < 9; ++i) motion[i] = R[i];
@@ -561,6 +583,18 @@ int oracle_svo_bucket(const int32_t* uv8, int n, int w, int h, const viso_svo_pa
 int oracle_svo_estimate(const int32_t* uv8, int n, int64_t frame, const viso_svo_params* p,
                         double* motion12, uint8_t* inlier) {
     return estimate(uv8, n, frame, *p, motion12, inlier);
+}
+
+// How the calling thread's last oracle_svo_estimate / oracle_svo_rig_estimate
+// ended: out5 = {exit code (ORACLE_SVO_EXIT_*), best hypothesis index, its
+// inlier count, 1 if another hypothesis reached that count, final inlier
+// count (-1 if the refinement was not reached)}.
+void oracle_svo_estimate_trace(int32_t out5[5]) {
+    out5[0] = g_trace.exit_code;
+    out5[1] = g_trace.best_h;
+    out5[2] = g_trace.best_cnt;
+    out5[3] = g_trace.best_shared;
+    out5[4] = g_trace.n_final;
 }
 
 // Rig motion from the matches of all cameras (camera of match i: cams[i]).

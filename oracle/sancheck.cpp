@@ -12,12 +12,15 @@
 // sanitizers armed: the monocular initialisation (FAST, KLT, 2D-2D RANSAC,
 // SelectMotion), stereo initialisation and tracking (direct pose, LK
 // alignment, keyframe insertion) in both summation orders, and the
-// multi-camera rig.  Exit status 0 and no sanitizer report = clean.
+// multi-camera rig; and the stereo VO spec's motion stage on its smallest
+// inputs (0..12 matches, every exit).
+// Exit status 0 and no sanitizer report = clean.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
+#include "../include/viso/viso_svo.h"
 #include "viso_oracle.h"
 
 namespace {
@@ -112,6 +115,63 @@ int run_rig(const Texture& tex) {
     return 0;
 }
 
+// Two of the late-failure inputs of tests/svo_cases.py (best hypothesis with 6
+// inliers, 5 after the refinement): {n, noise, seed} = {8, 1.0, 5}, sampler
+// frame 0, and {12, 1.5, 42}, frame 2.
+const int32_t kLate8[8 * 8] = {
+    990, 193, 978, 193, 983, 194, 971, 194, 74, 36, 54, 36, 96, 41, 74, 41, 1189, 321, 1170, 321, 1170, 316,
+    1152, 316, 93, 206, 79, 206, 107, 205, 93, 205, 1064, 96, 1051, 96, 1054, 97, 1042, 97, 21, 189, 8, 189,
+    35, 188, 23, 188, 400, 70, 388, 70, 404, 74, 394, 74, 404, 288, 375, 288, 417, 283, 387, 283};
+const int32_t kLate12[12 * 8] = {
+    547, 308, 535, 308, 551, 302, 536, 302, 963, 63, 951, 63, 955, 67, 946, 67, 1007, 169, 993, 169, 997, 170,
+    983, 170, 778, 274, 767, 274, 775, 274, 765, 274, 254, 176, 242, 176, 263, 177, 251, 177, 1181, 129, 1169,
+    129, 1169, 131, 1160, 131, 591, 96, 550, 96, 597, 103, 558, 103, 986, 150, 975, 150, 980, 152, 969, 152,
+    29, 284, -3, 284, 64, 276, 33, 276, 702, 67, 684, 67, 703, 69, 685, 69, 938, 233, 922, 233, 931, 233,
+    916, 233, 544, 92, 480, 92, 556, 100, 497, 100};
+
+// one estimate on exactly-sized heap buffers (an overrun is a report); a
+// failed estimate must leave the identity and a cleared mask
+int svo_estimate_once(const int32_t* uv8, int n, int64_t frame, const viso_svo_params& p, int want_exit) {
+    std::vector<int32_t> m(uv8, uv8 + (size_t)8 * n);
+    std::vector<uint8_t> inl((size_t)n, 0xAA);
+    std::vector<double> motion(12, -1.0);
+    const int rc = oracle_svo_estimate(m.data(), n, frame, &p, motion.data(), inl.data());
+    int32_t tr[5];
+    oracle_svo_estimate_trace(tr);
+    int cnt = 0;
+    for (uint8_t f : inl) cnt += f;
+    bool ok = rc == -1 ? cnt == 0 : (rc >= 6 && cnt == rc);
+    if (rc == -1)
+        for (int i = 0; i < 12; ++i) ok = ok && motion[(size_t)i] == ((i % 4 == 0 && i < 9) ? 1.0 : 0.0);
+    ok = ok && (want_exit < 0 || tr[0] == want_exit) && (rc >= 6) == (tr[0] == ORACLE_SVO_EXIT_OK ||
+                                                                      tr[0] == ORACLE_SVO_EXIT_REFINE_FAILED);
+    std::printf("svo estimate: n %d frame %d -> %d, exit %d, best %d (%d), final %d%s\n", n, (int)frame, rc, tr[0],
+                tr[1], tr[2], tr[4], ok ? "" : "  MISMATCH");
+    return ok ? 0 : 1;
+}
+
+int run_svo() {
+    viso_svo_params p;
+    oracle_svo_default_params(&p, 1242, 375, 718.856, 718.856, 607.19, 185.22, 0.54);
+    int rc = 0;
+    rc |= svo_estimate_once(kLate8, 8, 0, p, ORACLE_SVO_EXIT_FINAL_FEW);
+    rc |= svo_estimate_once(kLate12, 12, 2, p, ORACLE_SVO_EXIT_FINAL_FEW);
+    for (int n = 0; n <= 5; n += 5) rc |= svo_estimate_once(kLate12, n, 1, p, ORACLE_SVO_EXIT_FEW_MATCHES);
+    for (int n = 6; n <= 12; ++n) rc |= svo_estimate_once(kLate12, n, n, p, -1);
+    // two distinct matches six times over: every hypothesis is rank-deficient
+    std::vector<int32_t> two;
+    for (int r = 0; r < 6; ++r) two.insert(two.end(), kLate8, kLate8 + 16);
+    rc |= svo_estimate_once(two.data(), 12, 3, p, ORACLE_SVO_EXIT_NO_HYPOTHESIS);
+    // three distinct matches three times over ("rep3", {9, 1.0, 2}, frame 2):
+    // the best hypothesis keeps two of them, whose refinement is singular
+    const int32_t three[3 * 8] = {378, 293, 351, 293, 389, 290, 366, 290, 86,  112, 52,  112,
+                                  119, 117, 87,  117, 823, 162, 804, 162, 817, 163, 799, 163};
+    std::vector<int32_t> rep;
+    for (int r = 0; r < 3; ++r) rep.insert(rep.end(), three, three + 24);
+    rc |= svo_estimate_once(rep.data(), 9, 2, p, ORACLE_SVO_EXIT_REFINE_FAILED);
+    return rc;
+}
+
 }  // namespace
 
 int main() {
@@ -121,6 +181,7 @@ int main() {
     rc |= run_viso(tex, true, 0);
     rc |= run_viso(tex, true, 1);
     rc |= run_rig(tex);
+    rc |= run_svo();
     std::printf(rc ? "FAILED\n" : "sancheck ok\n");
     return rc;
 }

@@ -250,6 +250,25 @@ void oracle_rig_level_stats(const oracle_rig* r, double* out200);
 int oracle_photometric_ba(const uint8_t* const* kf_img, int n_kf, int w, int h, const double K[4], double* kf_poses,
                           double* points, const int32_t* host, int n, int iterations, double* report);
 
+// ---------------------------------------------------------------- stereo VO (SVO) spec
+// oracle_svo.cpp is the spec of include/viso/viso_svo.h (its entry points
+// take viso_svo_params and are bound by tests/oracle_lib.py).  The motion
+// stage, and the exit it took:
+struct viso_svo_params;
+void oracle_svo_default_params(struct viso_svo_params* p, int w, int h, double fx, double fy, double cu, double cv,
+                               double base);
+int oracle_svo_estimate(const int32_t* uv8, int n, int64_t frame, const struct viso_svo_params* p,
+                        double* motion12, uint8_t* inlier);
+#define ORACLE_SVO_EXIT_OK 0             /* a motion with >= 6 inliers */
+#define ORACLE_SVO_EXIT_FEW_MATCHES 1    /* fewer than 6 matches */
+#define ORACLE_SVO_EXIT_NO_HYPOTHESIS 2  /* no hypothesis with >= 6 inliers */
+#define ORACLE_SVO_EXIT_REFINE_FAILED 3  /* a refinement solve failed: the best hypothesis was kept and had >= 6 */
+#define ORACLE_SVO_EXIT_FINAL_FEW 4      /* the refined (or kept) motion has < 6 inliers */
+// {exit code, best hypothesis, its count, another hypothesis shares the
+// count, final count or -1} of the calling thread's last estimate.  The trace
+// is written beside the result and changes none.
+void oracle_svo_estimate_trace(int32_t out5[5]);
+
 #ifdef __cplusplus
 }
 #endif

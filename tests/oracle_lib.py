@@ -84,6 +84,7 @@ SIG = {
     "oracle_svo_match": ([_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i], _i),
     "oracle_svo_bucket": ([_vp, _i, _i, _i, _vp, _vp], _i),
     "oracle_svo_estimate": ([_vp, _i, ctypes.c_int64, _vp, _vp, _vp], _i),
+    "oracle_svo_estimate_trace": ([_vp], None),
     "oracle_svo_rig_estimate": ([_vp, _vp, _i, ctypes.c_int64, _vp, _vp, _vp, _vp], _i),
     "oracle_svo_sad_evals": ([_i], ctypes.c_uint64),
 }
@@ -501,6 +502,20 @@ def svo_estimate(uv8: np.ndarray, frame: int, p: SvoParams):
     inl = np.zeros(max(1, len(uv8)), np.uint8)
     n = lib.oracle_svo_estimate(ptr(uv8), len(uv8), frame, ctypes.byref(p), ptr(motion), ptr(inl))
     return motion, inl[:len(uv8)].astype(bool), n
+
+
+SVO_EXIT_OK, SVO_EXIT_FEW_MATCHES, SVO_EXIT_NO_HYPOTHESIS, SVO_EXIT_REFINE_FAILED, SVO_EXIT_FINAL_FEW = range(5)
+SVO_EXIT_NAMES = ("ok", "few_matches", "no_hypothesis", "refine_failed", "final_few")
+
+
+def svo_estimate_trace() -> dict:
+    """How this thread's last svo_estimate ended (oracle_svo_estimate_trace):
+    exit code, best hypothesis and its count, whether another hypothesis
+    shared that count, final inlier count (-1: refinement not reached)."""
+    out = np.zeros(5, np.int32)
+    load().oracle_svo_estimate_trace(ptr(out))
+    return dict(exit=int(out[0]), best_h=int(out[1]), best_cnt=int(out[2]), shared=bool(out[3]),
+                n_final=int(out[4]))
 
 
 class SvoSequence:

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import images, oracle_lib as ol
+from tests.svo_cases import synthetic_matches as _synthetic_matches
 
 
 def _params(w=1242, h=375, **kw):
@@ -69,31 +70,6 @@ def test_bucketing_keeps_lowest_indices():
     uv8[:, 5] = [10, 10, 10, 10, 60, 10]   # v_l2
     keep = ol.svo_bucket(uv8, 200, 100, p)
     assert keep.tolist() == [True, True, False, True, True, True]
-
-
-def _synthetic_matches(motion, n=300, seed=0, noise=0.0):
-    """Points in front of camera t-1 -> integer observations of both pairs."""
-    rng = np.random.default_rng(seed)
-    fx, fy, cu, cv, b = 718.856, 718.856, 607.19, 185.22, 0.54
-    R, t = motion[:9].reshape(3, 3), motion[9:]
-    out = []
-    while len(out) < n:
-        Z = rng.uniform(5, 40)
-        u1, v1 = rng.uniform(20, 1220), rng.uniform(20, 355)
-        d1 = np.round(fx * b / Z)
-        if d1 < 1:
-            continue
-        u1, v1 = np.round(u1), np.round(v1)
-        Zq = fx * b / d1
-        P = np.array([(u1 - cu) * Zq / fx, (v1 - cv) * Zq / fy, Zq])
-        Q = R @ P + t
-        if Q[2] <= 1:
-            continue
-        uL = fx * Q[0] / Q[2] + cu + rng.normal(0, noise)
-        vL = fy * Q[1] / Q[2] + cv + rng.normal(0, noise)
-        uR = fx * (Q[0] - b) / Q[2] + cu + rng.normal(0, noise)
-        out.append([u1, v1, u1 - d1, v1, np.round(uL), np.round(vL), np.round(uR), np.round(vL)])
-    return np.array(out, np.int32)
 
 
 def test_estimate_recovers_known_motion():

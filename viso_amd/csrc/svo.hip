@@ -1408,7 +1408,8 @@ __global__ __launch_bounds__(256) void svo_count_kernel(SvoDev p, PairArgs pa, i
 // ---------------------------------------------------------------- refine
 // One workgroup: best hypothesis (max count, lowest index), Gauss-Newton over
 // its inliers (sums: canonical tree over all M leaves, unselected = 0), final
-// inlier flags, motion, pose update T_wc <- T_wc * Tr^-1, stats.
+// inlier flags, motion, pose update T_wc <- T_wc * Tr^-1, stats.  A pair with
+// fewer than 6 final inliers fails: identity, 0 inliers, all flags 0.
 constexpr int kMaxChunks = 128;  // 64-leaf chunks: M <= 8192 (bucket count x bucket_max)
 
 constexpr int kRefineThreads = 256;  // 4 waves: up to 256 VGPRs per lane (fp64 leaves + 28 sums)
@@ -1528,6 +1529,10 @@ __global__ __launch_bounds__(kRefineThreads) void svo_refine_kernel(SvoDev p, Pa
         }
         atomicAdd(&s_cnt, c);
         __syncthreads();
+        // fewer than 6 inliers after the refinement: the pair fails, and a
+        // failed pair reports no inliers (each thread clears the flags it wrote)
+        if (s_cnt < 6)
+            for (int m = tid; m < M; m += kRefineThreads) inl[m] = 0;
     } else {
         for (int m = tid; m < M; m += kRefineThreads) inl[m] = 0;
     }
