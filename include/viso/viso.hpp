@@ -343,6 +343,19 @@ public:
         return out;
     }
 
+    // Pose refinement (viso_set_pose_refine): every tracking frame's direct
+    // pose is refined on its LK-aligned features (Huber-weighted
+    // Gauss-Newton on the reprojection error).  0 iterations = off.
+    void SetPoseRefine(int iterations, double huber_px = 1.0, double max_shift_px = 8.0) {
+        check(viso_set_pose_refine(ctx_, iterations, huber_px, max_shift_px), "viso_set_pose_refine");
+    }
+    // viso_get_pose_refine's report[8] (NaN before the first refinement)
+    std::array<double, 8> PoseRefine() const {
+        std::array<double, 8> report{};
+        check(viso_get_pose_refine(ctx_, report.data()), "viso_get_pose_refine");
+        return report;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

@@ -184,7 +184,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_STEREO 7
 #define VISO_KERNEL_UPLOAD 8 /* host -> device copy of a frame (viso_process_frame / _stereo) */
 #define VISO_KERNEL_MAPWIN 9 /* one retirement of the sliding-window map (viso_set_map_window) */
-#define VISO_KERNEL_COUNT 10
+#define VISO_KERNEL_REFINE 10 /* one frame's pose refinement (viso_set_pose_refine) */
+#define VISO_KERNEL_COUNT 11
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -364,6 +365,45 @@ int viso_map_retire(viso_ctx* ctx, int32_t width, int32_t height, const double p
                     const double* kf_poses, int32_t n_kf, const double* points, const int32_t* host,
                     int32_t n, int32_t cell, double* out_points, int32_t* out_host, uint8_t* keep,
                     size_t* n_out, int32_t counts[4]);
+
+/* Pose refinement (the repo's own spec, restated in tests/pose_refine_ref.py;
+ * DESIGN.md §Pose refinement): the third step of a semi-direct VO.  The
+ * reference computes, for every map point, the position at which its keyframe
+ * patch is found in the current image (LKAlignment, src/viso.cpp:121) and only
+ * draws it (src/viso.cpp:123-135).  With iterations > 0 every tracking frame's
+ * direct pose X is refined on those positions before anything reads it:
+ *  - point i is an observation when pair_kf[i] >= 0, success[i] != 0 and
+ *    |uv_after_i - uv_before_i|^2 <= max_shift_px^2 (the frame's LK row, as
+ *    viso_get_alignment gives it; computed at X);
+ *  - pass k = 0..iterations at T_k (T_0 = X): for every observation with
+ *    Pc.z > 0 the residual r = uv_after - projection, e = |r|, the 2x6 Jacobian
+ *    of dPixeldXi (src/viso.cpp:640-658), the Huber weight w = 1 (e <= huber_px)
+ *    or huber_px / e, rho = e^2 / 2 or huber_px (e - huber_px / 2); n_k the
+ *    observations used, cost_k = sum rho, H = sum w J^T J, b = sum w J^T r;
+ *  - in this order: n_0 < 6 -> X, status 1; for k >= 1, cost_k >= cost_{k-1}
+ *    -> T_{k-1}, status 3; k == iterations -> T_k, status 0; xi = H^-1 b not
+ *    finite -> T_k, status 2; else T_{k+1} = exp(xi) T_k.
+ * The refined pose replaces X in viso_get_poses, seeds the next frame's direct
+ * pose and is what a keyframe insertion, the BA and a retirement see;
+ * viso_get_alignment still reports the alignment computed at X.  One more
+ * launch per tracking frame; the frame's LK alignment runs at once on the
+ * context stream (no background or batched alignment while it is on).  fp64 in
+ * both precision modes.  iterations 0 (default) = off.  VISO_ERR_ARG unless
+ * iterations == 0, or 1 <= iterations <= 20, huber_px > 0 and
+ * max_shift_px > 0.  May be set while tracking: the next frame sees it. */
+int viso_set_pose_refine(viso_ctx* ctx, int32_t iterations, double huber_px, double max_shift_px);
+/* The last refined frame's report = {observations, steps applied, cost_0,
+ * cost at the result, inliers (e <= huber_px) at the result, status, rms of e
+ * at T_0, rms at the result}; all NaN before the first refinement. */
+int viso_get_pose_refine(viso_ctx* ctx, double report[8]);
+/* Stage entry (parity tests): one refinement on host data, by the launch of
+ * the frame path, with the context's intrinsics.  points: n x 3 world
+ * (0..16384); pair_kf, success, uv_before, uv_after: the LK row (n; uv n x 2).
+ * VISO_ERR_ARG on any out-of-range or NULL argument. */
+int viso_refine_pose(viso_ctx* ctx, const double* points, const int32_t* pair_kf, const uint8_t* success,
+                     const double* uv_before, const double* uv_after, int32_t n, const double pose_in[12],
+                     int32_t iterations, double huber_px, double max_shift_px, double pose_out[12],
+                     double report[8]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

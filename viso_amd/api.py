@@ -214,6 +214,27 @@ class Context:
         return {"points": out[:m.value].copy(), "host": oh[:m.value].copy(), "keep": keep[:n].copy(),
                 "n": int(m.value), "counts": [int(c) for c in counts]}
 
+    def refine_pose(self, points, pair_kf, success, uv_before, uv_after, pose_in, iterations: int = 5,
+                    huber_px: float = 1.0, max_shift_px: float = 8.0):
+        """viso_refine_pose: one pose refinement (viso_set_pose_refine) on
+        host data with the context's intrinsics: points (n, 3) world, the LK
+        row as ``lk_align`` returns it, pose_in 12 doubles (Tcw).  Returns
+        (pose (12,), report (8,))."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        pk = np.ascontiguousarray(pair_kf, dtype=np.int32).reshape(-1)
+        sc = np.ascontiguousarray(success, dtype=np.uint8).reshape(-1)
+        ub = np.ascontiguousarray(uv_before, dtype=np.float64).reshape(-1, 2)
+        ua = np.ascontiguousarray(uv_after, dtype=np.float64).reshape(-1, 2)
+        if not (pk.shape[0] == sc.shape[0] == ub.shape[0] == ua.shape[0] == n):
+            raise ValueError("refine_pose: one LK entry per point")
+        pin = np.ascontiguousarray(pose_in, dtype=np.float64).reshape(12)
+        out = np.zeros(12, np.float64)
+        rep = np.zeros(8, np.float64)
+        _lib.call("viso_refine_pose", self.h, _p(pts), _p(pk), _p(sc), _p(ub), _p(ua), n, _p(pin), int(iterations),
+                  float(huber_px), float(max_shift_px), _p(out), _p(rep))
+        return out, rep
+
     # ------------------------------------------------------------ timing
     def photometric_ba(self, kf_images, kf_poses, points, host, iterations: int = 5):
         """viso_photometric_ba: the BA of include/bundle_adjuster.h:22-106 on
@@ -258,6 +279,13 @@ def mono_points(cur_pyr, kf_pyr, width, height, pose_c, pose_k, points, cell=16,
 def map_retire(width, height, pose_c, kf_poses, points, host, cell=16, K=None, device: int = 0):
     """``Context.map_retire`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).map_retire(width, height, pose_c, kf_poses, points, host, cell)
+
+
+def refine_pose(points, pair_kf, success, uv_before, uv_after, pose_in, iterations=5, huber_px=1.0,
+                max_shift_px=8.0, width=640, height=480, K=None, device: int = 0):
+    """``Context.refine_pose`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).refine_pose(points, pair_kf, success, uv_before, uv_after,
+                                                                pose_in, iterations, huber_px, max_shift_px)
 
 
 def default_context(width: int = 640, height: int = 480, device: int = 0, K=None) -> Context:

@@ -357,6 +357,17 @@ struct viso_ctx {
     viso::DevBuf mapwin_buf;
     // *retired = false: nothing would be kept, map and keyframes unchanged
     int retire_keyframe(int cur, bool* retired);
+    // pose refinement (viso_set_pose_refine; refine.hip): every tracking
+    // frame's pose is refined on its own LK row — its final solve and its LK
+    // alignment (a batch of one) run at once on the context stream, then one
+    // refine launch — before anything reads the pose (the next frame's seed,
+    // an insertion, the pose log).  0 iterations = off.  refine_rep: the
+    // last frame's 8-double report (NaN until the first refinement)
+    int refine_iterations = 0;
+    double refine_huber = 0.0, refine_max_shift = 0.0;
+    viso::DevBuf refine_rep;
+    bool refine_on() const { return refine_iterations > 0; }
+    int refine_frame(int cur);
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

@@ -228,7 +228,7 @@ void viso_ctx::release() {
                       &kp1, &kp2, &kp1b, &kp2b, &track_success, &n_track_dev, &fast_rows,
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
-                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf};
+                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -647,8 +647,9 @@ int viso_ctx::host_lk_batch() const {
 
 int viso_ctx::finish_host_call() {
     // outside tracking, and with keyframe insertion (its decision reads the
-    // frame's nGood at once), as every other call
-    if (state != VISO_STATE_RUNNING || kf_on() || bg_active) return finish_call(lk_stream);
+    // frame's nGood at once) or pose refinement (every frame is finished
+    // inside on_new_frame), as every other call
+    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || bg_active) return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
     if ((int)lk_pending.size() > host_lk_batch()) return flush_lk_frames(lk_stream, true);
@@ -679,7 +680,7 @@ bool viso_ctx::host_queue_eligible() {
         const char* e = getenv("VISO_HOST_CHUNK");
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
-    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && bg_on() &&
+    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && bg_on() &&
            direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
@@ -801,7 +802,7 @@ int viso_ctx::stage_poses() {
 // frame of such a chunk is a tracking frame, so every ready flag is raised:
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
-                                      lk_tmpl.ptr && !kf_on() && !dpend && lk_pending.empty(); }
+                                      lk_tmpl.ptr && !kf_on() && !refine_on() && !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1413,6 +1414,14 @@ int viso_ctx::on_new_frame(int cur) {
                 }
             }
             ran_tracking = true;
+            // pose refinement (viso_set_pose_refine, refine.hip): this frame's
+            // final solve and its LK alignment now, then the refine launch on
+            // that LK row; everything below and the next frame see its pose
+            if (refine_on() && n_map > 0) {
+                int rc = finish_call(stream);
+                if (!rc) rc = refine_frame(cur);
+                if (rc) return rc;
+            }
             // keyframe insertion (stereo: oracle_viso.cpp; monocular:
             // monokf.hip): every interval-th tracking frame, one host sync
             // for its nGood

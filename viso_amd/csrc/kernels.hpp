@@ -234,6 +234,28 @@ size_t map_window_scratch_at(MapWinArgs& a, void* base, int w, int h, int cell, 
 // marks, claims, keep flags, the stable compaction and the counts
 void launch_map_retire(const MapWinArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- pose refinement
+// One frame's refinement on its LK row (viso_set_pose_refine, refine.hip):
+// everything in device memory, one launch of one workgroup.
+struct RefineArgs {
+    double K[4];               // fx, fy, cx, cy
+    const double* pts;         // n x 3 (world)
+    const int32_t* pair_kf;    // the LK row: n each (uv: n x 2)
+    const uint8_t* success;
+    const double* uv_before;
+    const double* uv_after;
+    int n;
+    int iterations;
+    double huber, max_shift;
+    const double* pose_in;     // 12, Tcw (may be pose_out)
+    double* pose_out;          // 12
+    double* log;               // the pose log (null: not logged), row log_index
+    double* log_host;          // its pinned host copy (device address) or null
+    int log_index;
+    double* report;            // 8
+};
+void launch_refine_pose(const RefineArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

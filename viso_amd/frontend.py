@@ -151,6 +151,24 @@ class Viso(FrameHandler):
             _lib.call("viso_get_point_hosts", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
         return out
 
+    def set_pose_refine(self, iterations: int, huber_px: float = 1.0, max_shift_px: float = 8.0) -> None:
+        """Pose refinement (viso_set_pose_refine): every tracking frame's
+        direct pose is refined on its LK-aligned features, `iterations`
+        Huber-weighted Gauss-Newton steps at most on the reprojection error of
+        the successful alignments that moved at most `max_shift_px`.
+        iterations 0 = off."""
+        _lib.call("viso_set_pose_refine", self.ctx.h, int(iterations), float(huber_px), float(max_shift_px))
+
+    def pose_refine(self) -> np.ndarray:
+        """viso_get_pose_refine: float64[8] = observations, steps applied,
+        cost at the direct pose, cost at the result, inliers at the result,
+        status (0 all passes run, 1 fewer than 6 observations, 2 non-finite
+        step, 3 the cost stopped falling), rms at the direct pose, rms at the
+        result; NaN before the first refinement."""
+        rep = np.zeros(8, np.float64)
+        _lib.call("viso_get_pose_refine", self.ctx.h, rep.ctypes.data)
+        return rep
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
