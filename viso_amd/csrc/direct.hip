@@ -271,8 +271,14 @@ struct RefSample {
     bool ok;
 };
 
-__device__ inline void ref_issue(const DirectArgs& a, const LevelPair& fp, int lv, int i,
-                                 RefSample& r) {
+// ref_issue in two steps, so that a wave prefetching two points can project
+// both (loads of the points and of the pose) before it issues the byte loads
+// of either: ref_project is everything up to the taps, ref_taps the taps.
+// `raw` given (the prefetch): the taps are loaded at clamped indices and
+// left as loaded, *raw bit k = tap k lies in the buffer; pf_store applies
+// ld_u8_or0's zero rule later, so that no select waits for these loads
+// between the issue of one point and of the next.
+__device__ inline void ref_project(const DirectArgs& a, const LevelPair& fp, int lv, int i, RefSample& r) {
     const int lane = threadIdx.x & 63;
     const int px = (lane >> 3) - 4, py = (lane & 7) - 4;
     const double scale = kScale[lv];
@@ -284,15 +290,40 @@ __device__ inline void ref_issue(const DirectArgs& a, const LevelPair& fp, int l
     const double hp = 4.0;
     r.ok = inside_px(r.ur - hp, r.vr - hp, w, h) && inside_px(r.ur + hp, r.vr + hp, w, h);
     const double x = r.ur + px, y = r.vr + py;
+    r.xx = x - floor(x);
+    r.yy = y - floor(y);
+}
+
+__device__ inline void ref_taps(const DirectArgs& a, const LevelPair& fp, int lv, RefSample& r,
+                                unsigned* raw = nullptr) {
+    const int lane = threadIdx.x & 63;
+    const int px = (lane >> 3) - 4, py = (lane & 7) - 4;
+    const int w = a.g.w[lv], h = a.g.h[lv];
+    const double x = r.ur + px, y = r.vr + py;
     const uint8_t* img = fp.last;
     const long long n = (long long)w * (long long)h;
     const long long base = r.ok ? (long long)(int)y * (long long)w + (long long)(int)x : -(1LL << 40);
-    r.t0 = ld_u8_or0(img, n, base);
-    r.t1 = ld_u8_or0(img, n, base + 1);
-    r.t2 = ld_u8_or0(img, n, base + w);
-    r.t3 = ld_u8_or0(img, n, base + w + 1);
-    r.xx = x - floor(x);
-    r.yy = y - floor(y);
+    if (raw) {
+        const long long i0 = base, i1 = base + 1, i2 = base + w, i3 = base + w + 1;
+        const bool in0 = i0 >= 0 && i0 < n, in1 = i1 >= 0 && i1 < n, in2 = i2 >= 0 && i2 < n,
+                   in3 = i3 >= 0 && i3 < n;
+        r.t0 = ld_global_u8(img, in0 ? i0 : 0);
+        r.t1 = ld_global_u8(img, in1 ? i1 : 0);
+        r.t2 = ld_global_u8(img, in2 ? i2 : 0);
+        r.t3 = ld_global_u8(img, in3 ? i3 : 0);
+        *raw = (in0 ? 1u : 0u) | (in1 ? 2u : 0u) | (in2 ? 4u : 0u) | (in3 ? 8u : 0u);
+    } else {
+        r.t0 = ld_u8_or0(img, n, base);
+        r.t1 = ld_u8_or0(img, n, base + 1);
+        r.t2 = ld_u8_or0(img, n, base + w);
+        r.t3 = ld_u8_or0(img, n, base + w + 1);
+    }
+}
+
+__device__ inline void ref_issue(const DirectArgs& a, const LevelPair& fp, int lv, int i,
+                                 RefSample& r) {
+    ref_project(a, fp, lv, i, r);
+    ref_taps(a, fp, lv, r);
 }
 
 __device__ inline void ref_finish(RefSample& r) {
@@ -303,11 +334,17 @@ __device__ inline void ref_finish(RefSample& r) {
                   : 0.0;
 }
 
-// Per-wave LDS window (16 x 16 bytes) of the current image around the
+// Per-wave LDS window (kCW x kCW bytes) of the current image around the
 // point's projection under a predicted T21 (the previous level's starting
-// pose), loaded while the prologue solves.  A sample whose four taps lie in
-// the window (itself inside the image, so no tap wraps a row or leaves the
-// buffer) reads the same bytes from LDS; any other takes sample_px's path.
+// pose), loaded while the prologue solves.  It is a window of the level's
+// *continuous buffer* (as the LK engines' followed window, track.hip
+// window_follow): origin (x0, y0) = (floor(u), floor(v)) - 9, not clamped to
+// the image, byte (r, c) = buf[(y0 + r) w + x0 + c], or 0 where that index
+// lies outside [0, w h).  Those are the bytes sample_px reads for a tap at
+// column x0 + c of row y0 + r, row wrap (a tap at column w is the next row's
+// first pixel) and zero rule (taps past the buffer) included, so a sample
+// whose four taps have window coordinates in [0, kCW) reads the same bytes
+// from LDS at the image's borders too; any other takes sample_px's path.
 constexpr int kCW = 20;  // window side: +-4..5 px of prediction error still hit
 constexpr int kCWBytes = kCW * kCW;
 constexpr int kCWLoads = (kCWBytes + 63) / 64;  // bytes per lane
@@ -316,6 +353,7 @@ struct CurWin {
     int x0, y0;
     bool on;
     uint8_t b[kCWLoads];  // this lane's bytes e = lane + 64 k of the row-major window
+    unsigned zero;        // bit k: byte k lies outside the buffer (b[k] is not its value: win_store writes 0)
 };
 
 __device__ inline void win_issue(const uint8_t* __restrict__ img, int w, int h, double u, double v,
@@ -323,19 +361,25 @@ __device__ inline void win_issue(const uint8_t* __restrict__ img, int w, int h, 
     c.on = w >= kCW && h >= kCW && u > -1e6 && u < 1e6 && v > -1e6 && v < 1e6;
     c.x0 = 0;
     c.y0 = 0;
+    c.zero = 0;
     if (!c.on) return;
-    int x0 = (int)floor(u) - kCW / 2 + 1;
-    int y0 = (int)floor(v) - kCW / 2 + 1;
-    x0 = min(max(x0, 0), w - kCW);
-    y0 = min(max(y0, 0), h - kCW);
+    const int x0 = (int)floor(u) - kCW / 2 + 1;
+    const int y0 = (int)floor(v) - kCW / 2 + 1;
     c.x0 = x0;
     c.y0 = y0;
+    const long long n = (long long)w * (long long)h;
+    const long long org = (long long)y0 * (long long)w + (long long)x0;
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < kCWLoads; ++k) {
         const int e = lane + 64 * k;
         const int r = e / kCW, col = e - r * kCW;
-        c.b[k] = ld_global_u8(img, (long long)(y0 + min(r, kCW - 1)) * w + x0 + col);
+        // ld_u8_or0's rule (one unsigned compare: i < 0 wraps past n); the
+        // zero is written by win_store, so no select waits for the load here
+        const long long i = org + (long long)(min(r, kCW - 1) * w + col);
+        const bool in = (unsigned long long)i < (unsigned long long)n;
+        c.b[k] = ld_global_u8(img, in ? i : 0);
+        c.zero |= in ? 0u : 1u << k;
     }
 }
 
@@ -344,7 +388,7 @@ __device__ inline void win_store(uint8_t* lds, const CurWin& c) {
 #pragma unroll
     for (int k = 0; k < kCWLoads; ++k) {
         const int e = lane + 64 * k;
-        if (e < kCWBytes) st_lds_u8(lds, e, c.b[k]);
+        if (e < kCWBytes) st_lds_u8(lds, e, (c.zero >> k) & 1u ? (uint8_t)0 : c.b[k]);
     }
 }
 
@@ -374,20 +418,6 @@ __device__ inline double sample_cw(const uint8_t* __restrict__ img, int w, int h
             const int o = (iy - c.y0) * kCW + (ix - c.x0);
             const double d0 = (double)ld_lds_u8(win, o), d1 = (double)ld_lds_u8(win, o + 1);
             const double d2 = (double)ld_lds_u8(win, o + kCW), d3 = (double)ld_lds_u8(win, o + kCW + 1);
-            const double xx = x - floor(x);
-            const double yy = y - floor(y);
-            return double((1 - xx) * (1 - yy) * d0 + xx * (1 - yy) * d1 + (1 - xx) * yy * d2 +
-                          xx * yy * d3);
-        }
-        // a sample on the image's last row: its lower taps lie past the
-        // level buffer and read 0 (sample_px's rule), the upper two come from
-        // the window (clamped to the bottom edge, it holds that row) — the
-        // points near the bottom edge, ~10 % of them at level 3, no longer
-        // wait for global loads
-        if (iy == h - 1 && ix >= c.x0 && ix + 1 < c.x0 + kCW && iy >= c.y0 && iy < c.y0 + kCW) {
-            const int o = (iy - c.y0) * kCW + (ix - c.x0);
-            const double d0 = (double)ld_lds_u8(win, o), d1 = (double)ld_lds_u8(win, o + 1);
-            const double d2 = 0.0, d3 = 0.0;
             const double xx = x - floor(x);
             const double yy = y - floor(y);
             return double((1 - xx) * (1 - yy) * d0 + xx * (1 - yy) * d1 + (1 - xx) * yy * d2 +
@@ -561,13 +591,21 @@ __device__ inline bool direct_point_rs(const DirectArgs& a, const LevelPair& fp,
     if (__builtin_expect(cw.on && fu - 6 >= cw.x0 && fu + 5 <= cw.x0 + kCW - 2 && fv - 6 >= cw.y0 &&
                              fv + 5 <= cw.y0 + kCW - 2,
                          1)) {
-        // uc - 6 .. uc + 6 (and vc's) in one binade: every lane's sample
-        // coordinate uc + px + {-1, 0, 1} is then exact, its int() is
-        // floor(uc) + px + {-1, 0, 1} (positive: the window test) and its
-        // fraction is exactly frac(uc), so all five samples of all lanes share
-        // one set of bilinear weights (the same products as the per-sample
-        // form) and read 12 distinct taps per lane
-        const bool one_binade = (__double_as_longlong(uc - 6.0) >> 52) == (__double_as_longlong(uc + 6.0) >> 52) &&
+        // uc - 6 .. uc + 6 (and vc's) non-negative and in one binade: every
+        // lane's sample coordinate uc + px + {-1, 0, 1} is then exact, its
+        // int() is floor(uc) + px + {-1, 0, 1} and its fraction is exactly
+        // frac(uc), so all five samples of all lanes share one set of bilinear
+        // weights (the same products as the per-sample form) and read 12
+        // distinct taps per lane.  The window's origin is not clamped, so the
+        // window test no longer keeps the coordinates positive: a point with
+        // uc in [4, 5) has gradient samples at uc - 5 in (-1, 0), where
+        // sample_px's int() base is 0 and floor() is -1 (and the fraction is
+        // taken from the negative coordinate), so such a point must take the
+        // per-sample form below.  uc >= 6 (vc >= 6) says so outright; the
+        // shifted compare alone would also refuse it, but only because a
+        // negative uc - 6 carries its sign bit into the shifted word.
+        const bool one_binade = uc >= 6.0 && vc >= 6.0 &&
+                                (__double_as_longlong(uc - 6.0) >> 52) == (__double_as_longlong(uc + 6.0) >> 52) &&
                                 (__double_as_longlong(vc - 6.0) >> 52) == (__double_as_longlong(vc + 6.0) >> 52);
         if (__builtin_expect(one_binade, 1)) {
             const double xx = uc - floor(uc), yy = vc - floor(vc);
@@ -751,7 +789,7 @@ __device__ inline float fast_lval(uint32_t t, double ur, double vr) {
 // Prologue prefetch of a whole tile, in LDS: per point j of the tile its
 // world point, its projection into the last frame (ur, vr, the bounds test)
 // and the four `last` patch taps of every lane (sample_px's bytes, packed),
-// and the 16 x 16 current-image window around its projection under the
+// and the kCW x kCW current-image window around its projection under the
 // predicted T21.  Issued while wave 0 solves, so after the solve the tiles
 // read nothing but LDS (and the rare sample outside its window).
 struct PfLds {
@@ -769,20 +807,27 @@ struct PfLds {
 struct PfPoint {
     RefSample r;
     CurWin c;
+    unsigned tin;   // ref_taps' raw-tap mask
+    double up, vp;  // projection under the predicted T21 (the window's centre)
 };
 
-__device__ inline void pf_issue(const DirectArgs& a, const LevelPair& fp, int lv, int i, const double* pred,
-                                bool ref, PfPoint& q) {
+// pf_project: the point, its `last` projection and its projection under the
+// predicted T21; pf_issue: the byte loads (the `last` taps, the window).
+__device__ inline void pf_project(const DirectArgs& a, const LevelPair& fp, int lv, int i, const double* pred,
+                                  bool ref, PfPoint& q) {
     if (ref) {
-        ref_issue(a, fp, lv, i, q.r);
+        ref_project(a, fp, lv, i, q.r);
     } else {
         q.r.P[0] = a.points[3 * i];
         q.r.P[1] = a.points[3 * i + 1];
         q.r.P[2] = a.points[3 * i + 2];
     }
-    double up, vp;
-    project_px(pred, a.K, q.r.P, kScale[lv], up, vp);
-    win_issue(fp.cur, a.g.w[lv], a.g.h[lv], up, vp, q.c);
+    project_px(pred, a.K, q.r.P, kScale[lv], q.up, q.vp);
+}
+
+__device__ inline void pf_issue(const DirectArgs& a, const LevelPair& fp, int lv, bool ref, PfPoint& q) {
+    if (ref) ref_taps(a, fp, lv, q.r, &q.tin);
+    win_issue(fp.cur, a.g.w[lv], a.g.h[lv], q.up, q.vp, q.c);
 }
 
 __device__ inline float fast_lval(uint32_t t, double ur, double vr);
@@ -790,9 +835,12 @@ __device__ inline float fast_lval(uint32_t t, double ur, double vr);
 template <bool LV16>
 __device__ inline void pf_store(int j, bool ref, const PfPoint& q, PfLds& pf) {
     const int lane = threadIdx.x & 63;
-    if (ref)
-        pf.taps[j][lane] = (uint32_t)q.r.t0 | ((uint32_t)q.r.t1 << 8) | ((uint32_t)q.r.t2 << 16) |
-                           ((uint32_t)q.r.t3 << 24);
+    if (ref) {
+        // ld_u8_or0's zero rule on the raw taps
+        const uint32_t t0 = q.tin & 1u ? (uint32_t)q.r.t0 : 0u, t1 = q.tin & 2u ? (uint32_t)q.r.t1 : 0u;
+        const uint32_t t2 = q.tin & 4u ? (uint32_t)q.r.t2 : 0u, t3 = q.tin & 8u ? (uint32_t)q.r.t3 : 0u;
+        pf.taps[j][lane] = t0 | (t1 << 8) | (t2 << 16) | (t3 << 24);
+    }
     if (LV16) pf.lv16[j][lane] = (_Float16)(q.r.ok ? fast_lval(pf.taps[j][lane], q.r.ur, q.r.vr) : 0.0f);
     if (q.c.on) win_store(pf.win[j], q.c);
     if (lane == 0) {
@@ -808,8 +856,10 @@ __device__ inline void pf_store(int j, bool ref, const PfPoint& q, PfLds& pf) {
     }
 }
 
-// Points j = first, first + stride, ... of tile b, two at a time (the loads
-// of both in flight together).  `pose_last` is the pose of the `last`
+// Points j = first, first + stride, ... of tile b, two at a time: both are
+// projected first (vmcnt counts in order, so a point or pose load issued
+// behind the first point's bytes would wait for them), then the byte loads
+// of both are in flight together.  `pose_last` is the pose of the `last`
 // projection: the `last` frame's own, or in a merged L(3) (whose `last` pose
 // is solved in this launch) a prediction, checked per lane in the tile phase.
 template <bool LV16 = false>
@@ -824,8 +874,10 @@ __device__ void prefetch_tile(const DirectArgs& a, int lv, int b, const double* 
         const int i0 = p0 + j, i1 = p0 + j2;
         const bool v0 = i0 < a.n, v1 = j2 < T && i1 < a.n;
         PfPoint q0{}, q1{};
-        if (v0) pf_issue(a, fp, lv, i0, pred, ref, q0);
-        if (v1) pf_issue(a, fp, lv, i1, pred, ref, q1);
+        if (v0) pf_project(a, fp, lv, i0, pred, ref, q0);
+        if (v1) pf_project(a, fp, lv, i1, pred, ref, q1);
+        if (v0) pf_issue(a, fp, lv, ref, q0);
+        if (v1) pf_issue(a, fp, lv, ref, q1);
         if (v0) pf_store<LV16>(j, ref, q0, pf);
         if (v1) pf_store<LV16>(j2, ref, q1, pf);
     }
