@@ -356,6 +356,28 @@ public:
         return report;
     }
 
+    // Map point culling (viso_set_point_cull): every map point keeps a track
+    // record {age, seen, found, fail_run} of its LK alignments; every
+    // interval-th tracking frame the points that failed max_fail_run frames
+    // in a row leave the map.  0 = off.
+    void SetPointCull(int interval, int max_fail_run = 3, double reproj_px = 2.0, int min_points = 50) {
+        check(viso_set_point_cull(ctx_, interval, max_fail_run, reproj_px, min_points), "viso_set_point_cull");
+    }
+    // viso_get_point_cull's info[8]
+    std::array<int64_t, 8> PointCull() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_point_cull(ctx_, info.data()), "viso_get_point_cull");
+        return info;
+    }
+    // every map point's track record {age, seen, found, fail_run}
+    std::vector<std::array<int32_t, 4>> PointTracks() const {
+        size_t n = 0;
+        check(viso_get_point_tracks(ctx_, nullptr, 0, &n), "viso_get_point_tracks");
+        std::vector<std::array<int32_t, 4>> out(n);
+        if (n) check(viso_get_point_tracks(ctx_, out.data()->data(), n, &n), "viso_get_point_tracks");
+        return out;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

@@ -185,7 +185,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_UPLOAD 8 /* host -> device copy of a frame (viso_process_frame / _stereo) */
 #define VISO_KERNEL_MAPWIN 9 /* one retirement of the sliding-window map (viso_set_map_window) */
 #define VISO_KERNEL_REFINE 10 /* one frame's pose refinement (viso_set_pose_refine) */
-#define VISO_KERNEL_COUNT 11
+#define VISO_KERNEL_CULL 11 /* the record update and cull launches (viso_set_point_cull) */
+#define VISO_KERNEL_COUNT 12
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -404,6 +405,66 @@ int viso_refine_pose(viso_ctx* ctx, const double* points, const int32_t* pair_kf
                      const double* uv_before, const double* uv_after, int32_t n, const double pose_in[12],
                      int32_t iterations, double huber_px, double max_shift_px, double pose_out[12],
                      double report[8]);
+
+/* Map point culling (the repo's own spec, restated in
+ * tests/point_cull_ref.py; DESIGN.md §Map point culling): a point whose
+ * keyframe patch keeps not being found leaves the map.  The reference computes
+ * the alignment of every map point in every tracking frame (LKAlignment,
+ * src/viso.cpp:768-843) and only draws it.  With interval > 0 every map point
+ * has a track record of four int32 {age, seen, found, fail_run}, zero when the
+ * point enters the map (initialisation, an insertion) and when the mode is
+ * switched on.
+ *  - Update, once per tracking frame, behind the frame's LK alignment (and its
+ *    refinement, viso_set_pose_refine), ahead of the insertion check, with the
+ *    frame's final pose T (as viso_get_poses) and its LK row (as
+ *    viso_get_alignment): age + 1; with pair_kf < 0 nothing else; otherwise
+ *    seen + 1 and the observation is good when success != 0, Pc = R P + t has
+ *    Pc.z > 0 and |uv_after - projection of Pc|^2 <= reproj_px^2; good:
+ *    found + 1, fail_run = 0; else fail_run + 1.
+ *  - Cull, on every interval-th tracking frame right behind its update: the
+ *    points with fail_run >= max_fail_run are candidates.  With none nothing
+ *    happens; when fewer than min_points would survive the cull is abandoned
+ *    (map and records unchanged); otherwise the survivors keep their order,
+ *    coordinates, hosts and records, the keyframes stay (also one that hosts
+ *    no point) and the LK templates are rebuilt.  The same frame's insertion
+ *    check sees the culled map.
+ * A retirement (viso_set_map_window) carries the kept points' records; the BA
+ * moves coordinates only.  One more launch per tracking frame, the frame's LK
+ * alignment at once on the context stream (no background or batched alignment
+ * while it is on); a cull frame is one more host synchronisation.  interval 0
+ * (default) = off.  VISO_ERR_ARG unless interval == 0, or interval >= 1,
+ * 1 <= max_fail_run <= 1000, reproj_px > 0 and 1 <= min_points <= 16384.  May
+ * be set while tracking: the next frame sees it. */
+int viso_set_point_cull(viso_ctx* ctx, int32_t interval, int32_t max_fail_run, double reproj_px,
+                        int32_t min_points);
+/* info = {interval, max_fail_run, culls applied, points culled in all, culls
+ * abandoned, and of the last applied cull: the number of frames processed
+ * before its frame (-1: none yet), the points it removed, the map size after
+ * it}. */
+int viso_get_point_cull(viso_ctx* ctx, int64_t info[8]);
+/* Every map point's track record (4 int32 each): the first min(cap, points)
+ * rows are written; *n = the point count.  VISO_ERR_STATE when the mode is
+ * off. */
+int viso_get_point_tracks(viso_ctx* ctx, int32_t* tracks4, size_t cap, size_t* n);
+/* Stage entry (parity tests): one update on host data, by the launch of the
+ * frame path, with the context's intrinsics.  points: n x 3 world (0..16384);
+ * pair_kf, success, uv_after: the LK row (n; uv n x 2); tracks4: n x 4, in and
+ * out; counts = {paired, good, failed, the longest fail_run after the update}.
+ * VISO_ERR_ARG on any out-of-range or NULL argument. */
+int viso_point_tracks_update(viso_ctx* ctx, const double* points, const int32_t* pair_kf, const uint8_t* success,
+                             const double* uv_after, int32_t n, const double pose[12], double reproj_px,
+                             int32_t* tracks4, int32_t counts[4]);
+/* Stage entry (parity tests): one cull on host data, by the launch of the
+ * frame path.  points: n x 3 (0..16384); host: n; tracks4: n x 4;
+ * 1 <= max_fail_run <= 1000, 0 <= min_points <= 16384.  Outputs: keep (n
+ * flags), out_points / out_host / out_tracks4 (the kept rows in order; room
+ * for n), *n_out = the number kept, counts = {candidates, survivors = n -
+ * candidates, n_out, abandoned}.  On abandonment *n_out = n, the outputs equal
+ * the inputs and every keep is 1.  VISO_ERR_ARG on any out-of-range or NULL
+ * argument. */
+int viso_points_cull(viso_ctx* ctx, const double* points, const int32_t* host, const int32_t* tracks4, int32_t n,
+                     int32_t max_fail_run, int32_t min_points, double* out_points, int32_t* out_host,
+                     int32_t* out_tracks4, uint8_t* keep, size_t* n_out, int32_t counts[4]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

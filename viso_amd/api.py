@@ -235,6 +235,48 @@ class Context:
                   float(huber_px), float(max_shift_px), _p(out), _p(rep))
         return out, rep
 
+    def point_tracks_update(self, points, pair_kf, success, uv_after, pose, tracks, reproj_px: float = 2.0):
+        """viso_point_tracks_update: one track-record update
+        (viso_set_point_cull) on host data with the context's intrinsics:
+        points (n, 3) world, the LK row as ``lk_align`` returns it, pose 12
+        doubles (Tcw), tracks (n, 4) int32.  Returns (tracks (n, 4), counts
+        [paired, good, failed, longest fail_run])."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        pk = np.ascontiguousarray(pair_kf, dtype=np.int32).reshape(-1)
+        sc = np.ascontiguousarray(success, dtype=np.uint8).reshape(-1)
+        ua = np.ascontiguousarray(uv_after, dtype=np.float64).reshape(-1, 2)
+        tr = np.array(tracks, dtype=np.int32, order="C").reshape(-1, 4)  # (a copy: updated in place)
+        if not (pk.shape[0] == sc.shape[0] == ua.shape[0] == tr.shape[0] == n):
+            raise ValueError("point_tracks_update: one LK entry and one record per point")
+        T = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        counts = np.zeros(4, np.int32)
+        _lib.call("viso_point_tracks_update", self.h, _p(pts), _p(pk), _p(sc), _p(ua), n, _p(T), float(reproj_px),
+                  _p(tr), _p(counts))
+        return tr, [int(c) for c in counts]
+
+    def cull_points(self, points, host, tracks, max_fail_run: int = 3, min_points: int = 50):
+        """viso_points_cull: one cull (viso_set_point_cull) on host data:
+        points (n, 3), host (n,), tracks (n, 4) int32.  Returns dict(points
+        (kept, 3), host (kept,), tracks (kept, 4), keep (n,), n kept, counts
+        [candidates, survivors, kept, abandoned])."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        hst = np.ascontiguousarray(host, dtype=np.int32).reshape(-1)
+        tr = np.ascontiguousarray(tracks, dtype=np.int32).reshape(-1, 4)
+        if not (hst.shape[0] == tr.shape[0] == n):
+            raise ValueError("cull_points: one host and one record per point")
+        out = np.zeros((max(n, 1), 3), np.float64)
+        oh = np.zeros(max(n, 1), np.int32)
+        ot = np.zeros((max(n, 1), 4), np.int32)
+        keep = np.zeros(max(n, 1), np.uint8)
+        counts = np.zeros(4, np.int32)
+        m = ctypes.c_size_t(0)
+        _lib.call("viso_points_cull", self.h, _p(pts), _p(hst), _p(tr), n, int(max_fail_run), int(min_points),
+                  _p(out), _p(oh), _p(ot), _p(keep), ctypes.byref(m), _p(counts))
+        return {"points": out[:m.value].copy(), "host": oh[:m.value].copy(), "tracks": ot[:m.value].copy(),
+                "keep": keep[:n].copy(), "n": int(m.value), "counts": [int(c) for c in counts]}
+
     # ------------------------------------------------------------ timing
     def photometric_ba(self, kf_images, kf_poses, points, host, iterations: int = 5):
         """viso_photometric_ba: the BA of include/bundle_adjuster.h:22-106 on
@@ -286,6 +328,19 @@ def refine_pose(points, pair_kf, success, uv_before, uv_after, pose_in, iteratio
     """``Context.refine_pose`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).refine_pose(points, pair_kf, success, uv_before, uv_after,
                                                                 pose_in, iterations, huber_px, max_shift_px)
+
+
+def point_tracks_update(points, pair_kf, success, uv_after, pose, tracks, reproj_px=2.0, width=640, height=480,
+                        K=None, device: int = 0):
+    """``Context.point_tracks_update`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).point_tracks_update(points, pair_kf, success, uv_after, pose,
+                                                                        tracks, reproj_px)
+
+
+def cull_points(points, host, tracks, max_fail_run=3, min_points=50, width=640, height=480, K=None,
+                device: int = 0):
+    """``Context.cull_points`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).cull_points(points, host, tracks, max_fail_run, min_points)
 
 
 def default_context(width: int = 640, height: int = 480, device: int = 0, K=None) -> Context:

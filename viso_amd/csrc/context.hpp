@@ -368,6 +368,23 @@ struct viso_ctx {
     viso::DevBuf refine_rep;
     bool refine_on() const { return refine_iterations > 0; }
     int refine_frame(int cur);
+    // map point culling (viso_set_point_cull; pointcull.hip): every map
+    // point's track record {age, seen, found, fail_run} is updated behind
+    // every tracking frame's LK row and final pose (the frame is finished
+    // inside on_new_frame, as for the refinement); every cull_interval-th
+    // tracking frame the points with fail_run >= cull_max_fail leave the map,
+    // unless fewer than cull_min_points would stay.  0 = off (pt_tracks
+    // null).  cull_last: {frames at the last applied cull (-1: none), the
+    // points it removed, the map size after it}
+    int cull_interval = 0, cull_max_fail = 0, cull_min_points = 0;
+    double cull_reproj = 0.0;
+    int64_t cull_applied = 0, cull_removed = 0, cull_abandoned = 0;
+    int64_t cull_last[3] = {-1, 0, 0};
+    viso::DevBuf pt_tracks, cull_buf;  // kMaxMapPoints records; the cull's scratch
+    bool cull_on() const { return cull_interval > 0; }
+    int tracks_zero(int first, int count);
+    int update_tracks(int cur);
+    int cull_points();
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

@@ -228,7 +228,8 @@ void viso_ctx::release() {
                       &kp1, &kp2, &kp1b, &kp2b, &track_success, &n_track_dev, &fast_rows,
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
-                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep};
+                      &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
+                      &pt_tracks, &cull_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -647,9 +648,10 @@ int viso_ctx::host_lk_batch() const {
 
 int viso_ctx::finish_host_call() {
     // outside tracking, and with keyframe insertion (its decision reads the
-    // frame's nGood at once) or pose refinement (every frame is finished
-    // inside on_new_frame), as every other call
-    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || bg_active) return finish_call(lk_stream);
+    // frame's nGood at once), pose refinement or point culling (every frame
+    // is finished inside on_new_frame), as every other call
+    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || bg_active)
+        return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
     if ((int)lk_pending.size() > host_lk_batch()) return flush_lk_frames(lk_stream, true);
@@ -680,7 +682,7 @@ bool viso_ctx::host_queue_eligible() {
         const char* e = getenv("VISO_HOST_CHUNK");
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
-    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && bg_on() &&
+    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && bg_on() &&
            direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
@@ -802,7 +804,8 @@ int viso_ctx::stage_poses() {
 // frame of such a chunk is a tracking frame, so every ready flag is raised:
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
-                                      lk_tmpl.ptr && !kf_on() && !refine_on() && !dpend && lk_pending.empty(); }
+                                      lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !dpend &&
+                                      lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1117,6 +1120,8 @@ int viso_ctx::append_keyframe(int cur, int m) {
     VISO_HIP_CHECK(hipMemcpyAsync((char*)kf_poses.ptr + 96 * (kf_slots.size() - 1), pose_of(cur), 96,
                                   hipMemcpyDeviceToDevice, stream));
     point_host.resize((size_t)n_map, (int32_t)kf_slots.size() - 1);
+    rc = tracks_zero(n_map - m, m);
+    if (rc) return rc;
     if (ba_iterations > 0) {
         rc = bundle_adjust();
         if (rc) return rc;
@@ -1145,6 +1150,8 @@ int viso_ctx::stereo_init(int cur, bool* made) {
     hold(cur);
     n_map = std::min(m, kMaxMapPoints);
     point_host.assign((size_t)n_map, 0);
+    rc = tracks_zero(0, n_map);
+    if (rc) return rc;
     VISO_HIP_CHECK(hipMemcpyAsync(kf_poses.ptr, pose_of(cur), 96, hipMemcpyDeviceToDevice, stream));
     rc = build_lk_templates();
     if (rc) return rc;
@@ -1313,6 +1320,7 @@ int viso_ctx::on_new_frame(int cur) {
                     std::memcpy(pose + 9, initT, sizeof(initT));
                     n_map = std::min(nr_inliers, kMaxMapPoints);
                     point_host.assign((size_t)n_map, 0);  // in keyframe 0's (ref) frame
+                    if (const int rc = tracks_zero(0, n_map)) return rc;
                     // the frame's pose, the map points and the two keyframe
                     // poses in one launch (round 4: a kernel and three copies)
                     launch_map_create(pose_of(cur), pose, geo.points_out, (double*)map_pts.ptr, n_map,
@@ -1417,15 +1425,26 @@ int viso_ctx::on_new_frame(int cur) {
             // pose refinement (viso_set_pose_refine, refine.hip): this frame's
             // final solve and its LK alignment now, then the refine launch on
             // that LK row; everything below and the next frame see its pose
-            if (refine_on() && n_map > 0) {
+            if ((refine_on() || cull_on()) && n_map > 0) {
                 int rc = finish_call(stream);
-                if (!rc) rc = refine_frame(cur);
+                if (!rc && refine_on()) rc = refine_frame(cur);
+                // map point culling (viso_set_point_cull, pointcull.hip):
+                // every point's track record on this frame's LK row at its
+                // final pose
+                if (!rc && cull_on()) rc = update_tracks(cur);
                 if (rc) return rc;
             }
             // keyframe insertion (stereo: oracle_viso.cpp; monocular:
             // monokf.hip): every interval-th tracking frame, one host sync
             // for its nGood
             ++track_cnt;
+            // every cull_interval-th tracking frame the points that kept
+            // failing leave the map, ahead of the insertion check (one host
+            // sync)
+            if (cull_on() && n_map > 0 && track_cnt % cull_interval == 0) {
+                const int rc = cull_points();
+                if (rc) return rc;
+            }
             stats[15] = (double)kf_slots.size();  // before a possible insertion, as the oracle
             const bool mono_kf = mkf_interval > 0;
             const int interval = mono_kf ? mkf_interval : (right_l0 && stereo_base > 0) ? kf_interval : 0;

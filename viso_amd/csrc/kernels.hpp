@@ -228,6 +228,10 @@ struct MapWinArgs {
     uint8_t* keep;          // n
     int* out_host;          // kept points' hosts and coordinates, in index order
     double* out_pts;
+    // the points' track records (viso_set_point_cull), or null: a kept
+    // point's row moves with it into out_rec
+    const int4* rec;
+    int4* out_rec;
 };
 size_t map_window_scratch_bytes(int w, int h, int cell, int cap_points);
 size_t map_window_scratch_at(MapWinArgs& a, void* base, int w, int h, int cell, int cap_points);
@@ -255,6 +259,37 @@ struct RefineArgs {
     double* report;            // 8
 };
 void launch_refine_pose(const RefineArgs& a, hipStream_t stream);
+
+// ---------------------------------------------------------------- map point culling
+// One frame's track-record update and one cull of viso_set_point_cull
+// (pointcull.hip): everything in device memory.  A record is {age, seen,
+// found, fail_run}.
+struct PointCullArgs {
+    double K[4];              // fx, fy, cx, cy
+    const double* pts;        // n x 3 (world)
+    int n;
+    // the update: the frame's LK row, its final pose, the bound
+    const int32_t* pair_kf;
+    const uint8_t* success;
+    const double* uv_after;   // n x 2
+    const double* pose;       // 12, Tcw
+    double reproj;            // pixels
+    int4* tracks;             // n records, in place (the cull only reads them)
+    int* fcounts;             // {paired, good, failed, longest fail_run}; zero before the launch
+    // the cull
+    const int* host;          // n host keyframe indices
+    int max_fail_run, min_points;
+    uint8_t* keep;            // n
+    double* out_pts;          // the kept points, hosts and records in index order
+    int* out_host;
+    int4* out_tracks;
+    int* ccounts;             // {candidates, survivors, kept, abandoned}
+};
+// scratch of one cull (keep flags and the compacted map) for n points
+size_t point_cull_scratch_bytes(int n);
+size_t point_cull_scratch_at(PointCullArgs& a, void* base, int n);
+void launch_point_tracks(const PointCullArgs& a, hipStream_t stream);
+void launch_point_cull(const PointCullArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;

@@ -92,8 +92,9 @@ __global__ __launch_bounds__(256) void mapwin_claim_kernel(MapWinArgs a) {
 
 // (3) keep flags and the stable compaction (one workgroup), then the pose
 // rows: kept points and their new hosts in index order into out_pts /
-// out_host; counts[3] = survivors, counts[4] = kept; with something kept and
-// shift_poses set, keyframe pose row k + 1 moves to row k
+// out_host (and, with track records, their rows into out_rec); counts[3] =
+// survivors, counts[4] = kept; with something kept and shift_poses set,
+// keyframe pose row k + 1 moves to row k
 __global__ __launch_bounds__(1024) void mapwin_compact_kernel(MapWinArgs a) {
     __shared__ int s_w[16], s_s[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,6 +134,7 @@ __global__ __launch_bounds__(1024) void mapwin_compact_kernel(MapWinArgs a) {
             a.out_pts[3 * j + 1] = a.pts[3 * (size_t)i + 1];
             a.out_pts[3 * j + 2] = a.pts[3 * (size_t)i + 2];
             a.out_host[j] = nh;
+            if (a.rec) a.out_rec[j] = a.rec[i];
         }
         base += tot;
     }
@@ -162,7 +164,7 @@ size_t map_window_scratch_at(MapWinArgs& a, void* base, int w, int h, int cell, 
     // (marks and counts share the zero fill)
     const size_t o_cnt = b.take(32), o_mark = b.take(4 * cells), o_zero_end = b.off, o_win = b.take(4 * cells),
                  o_pc = b.take(4 * n), o_nh = b.take(4 * n), o_keep = b.take(n), o_oh = b.take(4 * n),
-                 o_op = b.take(24 * n);
+                 o_op = b.take(24 * n), o_or = b.take(16 * n);
     if (base) {
         char* p = (char*)base;
         a.w = w;
@@ -179,6 +181,7 @@ size_t map_window_scratch_at(MapWinArgs& a, void* base, int w, int h, int cell, 
         a.keep = (uint8_t*)(p + o_keep);
         a.out_host = (int*)(p + o_oh);
         a.out_pts = (double*)(p + o_op);
+        a.out_rec = (int4*)(p + o_or);
     }
     return b.off;
 }
@@ -229,6 +232,7 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     a.pts = (const double*)map_pts.ptr;
     a.host = (const int*)point_host_dev.ptr;
     a.n = n;
+    a.rec = cull_on() ? (const int4*)pt_tracks.ptr : nullptr;  // (viso_set_point_cull: a kept point's record moves with it)
     if (n > 0)
         VISO_HIP_CHECK(hipMemcpyAsync(point_host_dev.ptr, point_host.data(), 4 * (size_t)n, hipMemcpyHostToDevice,
                                       stream));
@@ -245,6 +249,8 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     const int kept = std::max(0, std::min(h_int[12], n));
     if (kept == 0) return VISO_OK;
     VISO_HIP_CHECK(hipMemcpyAsync(map_pts.ptr, a.out_pts, 24 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
+    if (a.rec)
+        VISO_HIP_CHECK(hipMemcpyAsync(pt_tracks.ptr, a.out_rec, 16 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
     point_host.assign(hosts.begin(), hosts.begin() + kept);
     n_map = kept;
     // the slot's readers on lk_stream are its lk_use batch, those on the

@@ -36,8 +36,8 @@ struct RoctxRange {
 inline const char* phase_name(int kernel) {
     static const char* const names[] = {"viso:pyramid", "viso:fast",  "viso:klt",    "viso:ransac",
                                         "viso:select",  "viso:direct", "viso:lkalign", "viso:stereo",
-                                        "viso:upload",  "viso:mapwin", "viso:refine"};
-    return (kernel >= 0 && kernel < 11) ? names[kernel] : "viso:phase";
+                                        "viso:upload",  "viso:mapwin", "viso:refine", "viso:cull"};
+    return (kernel >= 0 && kernel < 12) ? names[kernel] : "viso:phase";
 }
 
 }  // namespace viso

@@ -169,6 +169,36 @@ class Viso(FrameHandler):
         _lib.call("viso_get_pose_refine", self.ctx.h, rep.ctypes.data)
         return rep
 
+    def set_point_cull(self, interval: int, max_fail_run: int = 3, reproj_px: float = 2.0,
+                       min_points: int = 50) -> None:
+        """Map point culling (viso_set_point_cull): every map point keeps a
+        track record {age, seen, found, fail_run} of its LK alignments; every
+        `interval`-th tracking frame the points whose alignment failed (or
+        landed more than `reproj_px` from their projection) `max_fail_run`
+        frames in a row leave the map, unless fewer than `min_points` would
+        stay.  interval 0 = off."""
+        _lib.call("viso_set_point_cull", self.ctx.h, int(interval), int(max_fail_run), float(reproj_px),
+                  int(min_points))
+
+    def point_cull(self) -> np.ndarray:
+        """viso_get_point_cull: int64[8] = interval, max_fail_run, culls
+        applied, points culled in all, culls abandoned, then of the last
+        applied cull: frames processed before its frame (-1: none yet), the
+        points it removed, the map size after it."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_point_cull", self.ctx.h, info.ctypes.data)
+        return info
+
+    def point_tracks(self) -> np.ndarray:
+        """Every map point's track record (viso_get_point_tracks): int32
+        (points, 4) = age, seen, found, fail_run."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_point_tracks", self.ctx.h, None, 0, ctypes.byref(n))
+        out = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            _lib.call("viso_get_point_tracks", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
+        return out
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
