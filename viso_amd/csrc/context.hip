@@ -106,6 +106,7 @@ int viso_create(const viso_params* p, int device, viso_ctx** out) {
     c->device = device;
     if (const char* e = getenv("VISO_HOST_TIMES")) c->host_times.on = c->stage.timed = e[0] == '1';
     if (const char* e = getenv("VISO_HOST_TIMELINE")) c->dev_tl.on = e[0] == '1';
+    if (const char* e = getenv("VISO_DIRECT_SCALAR_PASS")) c->direct_scalar_pass = e[0] != '0';
     c->geom = make_geom(p->width, p->height);
     if (c->create_streams() != VISO_OK) {
         delete c;
@@ -326,7 +327,8 @@ int viso_direct_pose(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_py
                            frame_from_base((const uint8_t*)(base + o_c), g), g, K,
                            (const double*)(base + o_p), n, (const double*)(base + o_pl),
                            (const double*)(base + o_pio), direct_scratch_at(base + o_ds), nullptr,
-                           (double*)(base + o_pio), nullptr, -1, c->stream, c->p.precision);
+                           (double*)(base + o_pio), nullptr, -1, c->stream, c->p.precision,
+                           c->direct_scalar_pass);
     }
     VISO_HIP_CHECK(hipGetLastError());
     VISO_HIP_CHECK(hipMemcpyAsync(pose_io, base + o_pio, 96, hipMemcpyDeviceToHost, c->stream));

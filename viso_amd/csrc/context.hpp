@@ -267,6 +267,9 @@ struct viso_ctx {
     hipStream_t lk_stream = nullptr;
     hipEvent_t lk_ring[viso::kLkRing] = {};  // recorded after each lk_stream batch
     viso::HostStage stage;  // pinned staging of host-ingested frames (ingest_host)
+    // direct pose: the helper waves' scalar pass (VISO_DIRECT_SCALAR_PASS=0
+    // at creation keeps every tile's scalars in its point waves)
+    bool direct_scalar_pass = true;
     viso::HostTimes host_times;
     viso::DevTimeline dev_tl;
     // Host uploads run on their own stream (created at the first one, with a

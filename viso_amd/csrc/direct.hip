@@ -437,14 +437,77 @@ __device__ inline double sample_cw(const uint8_t* __restrict__ img, int w, int h
 // stay in their lanes (the return value; 0 in lanes >= 12).
 //   0: x / z, 1: y / z (the projection)        -> Q[0], Q[1]
 //   2..11: J[0], J[2], J[3], J[4], J[5], J[7], J[8], J[9], J[10], J[11]
-__device__ inline double point_quotients(const Intrinsics& K, const double* pose, const double* P, double scale,
-                                         double* Q, double* qt) {
-    const int lane = threadIdx.x & 63;
+//
+// quotient_slot is the table form for one lane: quotient k < 12 of point P,
+// the operands taken from the twelve-value table qt of that point (written
+// by the point's `lead` lane; every lane that shares qt passes the same P).
+// The tile phase has one point and one table per wave (point_quotients).
+// quotient_select picks the same operands by selects on k; the helper
+// waves' scalar pass, five points of 12 lanes each, uses it (scalar_pass).
+__device__ inline double quotient_slot(const Intrinsics& K, const double* pose, const double* P, double scale, int k,
+                                       bool lead, double* qt) {
     double Pc[3];
     mat3_vec(pose, P, Pc);
     const double x = Pc[0] + pose[9], y = Pc[1] + pose[10], z = Pc[2] + pose[11];
     const double fx = K.fx * scale, fy = K.fy * scale;
     const double zz = z * z, xy = x * y;
+    const double fxx = fx * x, fyy = fy * y;
+    // slots: 0 x, 1 y, 2 fx, 3 -fx, 4 fxx, 5 fy, 6 -fy, 7 fyy, 8 1.0, 9 xy, 10 z, 11 zz
+    if (lead) {
+        double2* t2 = reinterpret_cast<double2*>(qt);
+        t2[0] = make_double2(x, y);
+        t2[1] = make_double2(fx, -fx);
+        t2[2] = make_double2(fxx, fy);
+        t2[3] = make_double2(-fy, fyy);
+        t2[4] = make_double2(1.0, xy);
+        t2[5] = make_double2(z, zz);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // per-quotient slots, 4 bits each
+    constexpr unsigned long long kC1 = 0x557653433210ULL, kC2 = 0x091181090888ULL, kDen = 0xABBBAABBBAAAULL;
+    const double c1 = qt[(kC1 >> (4 * k)) & 15];
+    const double c2 = qt[(kC2 >> (4 * k)) & 15];
+    const double den = qt[(kDen >> (4 * k)) & 15];
+    double q = (c1 * c2) / den;
+    if (k == 5) q = fx + q;
+    if (k == 9) q = -fy - q;
+    return q;
+}
+
+// the same quotient with the operands chosen by selects on k (no table)
+__device__ inline double quotient_select(const Intrinsics& K, const double* pose, const double* P, double scale,
+                                         int k) {
+    double Pc[3];
+    mat3_vec(pose, P, Pc);
+    const double x = Pc[0] + pose[9], y = Pc[1] + pose[10], z = Pc[2] + pose[11];
+    const double fx = K.fx * scale, fy = K.fy * scale;
+    const double zz = z * z, xy = x * y;
+    const double fxx = fx * x, fyy = fy * y;
+    double c1, c2, den;
+    c1 = fy;
+    c1 = k == 0 ? x : c1;
+    c1 = k == 1 ? y : c1;
+    c1 = k == 2 ? fx : c1;
+    c1 = (k == 3 || k == 4 || k == 6) ? -fx : c1;
+    c1 = k == 5 ? fxx : c1;
+    c1 = k == 8 ? -fy : c1;
+    c1 = k == 9 ? fyy : c1;
+    c2 = 1.0;
+    c2 = (k == 3 || k == 5 || k == 11) ? x : c2;
+    c2 = (k == 4 || k == 10) ? xy : c2;
+    c2 = (k == 6 || k == 8 || k == 9) ? y : c2;
+    den = (k <= 2 || k == 6 || k == 7 || k == 11) ? z : zz;
+    double q = (c1 * c2) / den;
+    if (k == 5) q = fx + q;
+    if (k == 9) q = -fy - q;
+    return q;
+}
+
+__device__ inline double point_quotients(const Intrinsics& K, const double* pose, const double* P, double scale,
+                                         double* Q, double* qt) {
+    const int lane = threadIdx.x & 63;
     // numerator = c1 * c2 (c2 = 1.0 where the numerator is a single value:
     // exact), denominator z or zz, per lane:
     //    0: x / z                1: y / z               2: fx / z      (J[0])
@@ -453,52 +516,13 @@ __device__ inline double point_quotients(const Intrinsics& K, const double* pose
     //    9: fy*y * y / zz (J[9]) 10: fy * xy / zz (J[10]) 11: fy * x / z (J[11])
     // The operands come from a per-wave table of the twelve candidate values
     // in LDS, each lane reading its three at fixed per-lane slots (qt given:
-    // the tile phase), or by lane-mask selects (26 v_cndmask: the tile phase
-    // is VALU-issue-bound, LDS reads are not VALU; -0.6 us per frame,
-    // profiles/r05_quotient_table_ab.log).  The twelve results go to every
-    // lane by readlane (passing J's ten back through the table measured the
-    // same).
-    const double fxx = fx * x, fyy = fy * y;
-    double c1, c2, den;
-    if (qt) {
-        // slots: 0 x, 1 y, 2 fx, 3 -fx, 4 fxx, 5 fy, 6 -fy, 7 fyy, 8 1.0, 9 xy, 10 z, 11 zz
-        if (lane == 0) {
-            double2* t2 = reinterpret_cast<double2*>(qt);
-            t2[0] = make_double2(x, y);
-            t2[1] = make_double2(fx, -fx);
-            t2[2] = make_double2(fxx, fy);
-            t2[3] = make_double2(-fy, fyy);
-            t2[4] = make_double2(1.0, xy);
-            t2[5] = make_double2(z, zz);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // per-lane slots, 4 bits each, lanes 0..11 (lanes >= 12 as lane 11)
-        constexpr unsigned long long kC1 = 0x557653433210ULL, kC2 = 0x091181090888ULL,
-                                     kDen = 0xABBBAABBBAAAULL;
-        const int l = lane < 12 ? lane : 11;
-        c1 = qt[(kC1 >> (4 * l)) & 15];
-        c2 = qt[(kC2 >> (4 * l)) & 15];
-        den = qt[(kDen >> (4 * l)) & 15];
-    } else {
-        c1 = fy;
-        c1 = lane == 0 ? x : c1;
-        c1 = lane == 1 ? y : c1;
-        c1 = lane == 2 ? fx : c1;
-        c1 = (lane == 3 || lane == 4 || lane == 6) ? -fx : c1;
-        c1 = lane == 5 ? fxx : c1;
-        c1 = lane == 8 ? -fy : c1;
-        c1 = lane == 9 ? fyy : c1;
-        c2 = 1.0;
-        c2 = (lane == 3 || lane == 5 || lane >= 11) ? x : c2;
-        c2 = (lane == 4 || lane == 10) ? xy : c2;
-        c2 = (lane == 6 || lane == 8 || lane == 9) ? y : c2;
-        den = (lane <= 2 || lane == 6 || lane == 7 || lane >= 11) ? z : zz;
-    }
-    double q = (c1 * c2) / den;
-    if (lane == 5) q = fx + q;
-    if (lane == 9) q = -fy - q;
+    // the tile phase; lanes >= 12 as lane 11), or by lane-mask selects (26
+    // v_cndmask: the tile phase is VALU-issue-bound, LDS reads are not VALU;
+    // -0.6 us per frame, profiles/r05_quotient_table_ab.log).  The twelve
+    // results go to every lane by readlane (passing J's ten back through the
+    // table measured the same).
+    const int k = lane < 12 ? lane : 11;
+    const double q = qt ? quotient_slot(K, pose, P, scale, k, lane == 0, qt) : quotient_select(K, pose, P, scale, k);
     // the projection to every lane; J's ten stay in lanes 2..11 (the factored
     // sums fetch them per lane, direct_point_rs), lanes >= 12 hold J's zeros
     Q[0] = readlane_f64(q, 0);
@@ -559,6 +583,139 @@ __device__ inline double reduce_scatter_6_desc(const double* v) {
     return d;
 }
 
+// The current-image classes of a good point (direct_point_rs decides them in
+// the wave, scalar_pass on a helper wave): how its five samples are read.
+enum : int {
+    kClsOut = 0,       // the current-image side of `good` fails
+    kClsShared = 1,    // whole patch in the window, one binade: shared weights
+    kClsStraddle = 2,  // whole patch in the window: per-sample weights, LDS taps
+    kClsSample = 3,    // sample_cw decides per sample
+};
+
+// Whole patch in the window (wave-uniform, conservative: every lane's
+// samples at x, x +- 1 have int() bases in [floor(uc) - 6, floor(uc) + 5],
+// likewise in y): the five samples read LDS with no per-lane tests;
+// otherwise sample_cw decides per sample.
+__device__ inline bool patch_in_window(bool on, int x0, int y0, int fu, int fv) {
+    return on && fu - 6 >= x0 && fu + 5 <= x0 + kCW - 2 && fv - 6 >= y0 && fv + 5 <= y0 + kCW - 2;
+}
+
+// uc - 6 .. uc + 6 (and vc's) non-negative and in one binade: every
+// lane's sample coordinate uc + px + {-1, 0, 1} is then exact, its
+// int() is floor(uc) + px + {-1, 0, 1} and its fraction is exactly
+// frac(uc), so all five samples of all lanes share one set of bilinear
+// weights (the same products as the per-sample form) and read 12
+// distinct taps per lane.  The window's origin is not clamped, so the
+// window test no longer keeps the coordinates positive: a point with
+// uc in [4, 5) has gradient samples at uc - 5 in (-1, 0), where
+// sample_px's int() base is 0 and floor() is -1 (and the fraction is
+// taken from the negative coordinate), so such a point must take the
+// per-sample form.  uc >= 6 (vc >= 6) says so outright; the
+// shifted compare alone would also refuse it, but only because a
+// negative uc - 6 carries its sign bit into the shifted word.
+__device__ inline bool patch_one_binade(double uc, double vc) {
+    return uc >= 6.0 && vc >= 6.0 &&
+           (__double_as_longlong(uc - 6.0) >> 52) == (__double_as_longlong(uc + 6.0) >> 52) &&
+           (__double_as_longlong(vc - 6.0) >> 52) == (__double_as_longlong(vc + 6.0) >> 52);
+}
+
+// error and gradient of this lane's pixel, class kClsShared: the bilinear
+// weights w00..w11 of frac(uc), frac(vc) serve all five samples
+__device__ inline void samples_shared(const uint8_t* win, const CurWin& cw, int fu, int fv, double w00, double w10,
+                                      double w01, double w11, double lval, double& error, double& g0,
+                                      double& g1) {
+    const int lane = threadIdx.x & 63;
+    const int px = (lane >> 3) - 4, py = (lane & 7) - 4;
+    // tap (-1, -1) of this lane: every tap below is a non-negative
+    // immediate offset from it (one address, twelve ds_read_u8)
+    const uint8_t* wb = win + ((fv + py - 1 - cw.y0) * kCW + (fu + px - 1 - cw.x0));
+    auto tap = [&](int dx, int dy) { return (double)ld_lds_u8(wb, (dy + 1) * kCW + (dx + 1)); };
+    const double tm0 = tap(-1, 0), t00 = tap(0, 0), t10 = tap(1, 0), t20 = tap(2, 0);
+    const double tm1 = tap(-1, 1), t01 = tap(0, 1), t11 = tap(1, 1), t21 = tap(2, 1);
+    const double t0m = tap(0, -1), t1m = tap(1, -1), t02 = tap(0, 2), t12 = tap(1, 2);
+    auto bil = [&](double d0, double d1, double d2, double d3) {
+        return double(w00 * d0 + w10 * d1 + w01 * d2 + w11 * d3);
+    };
+    error = lval - bil(t00, t10, t01, t11);
+    // GetGradient (include/keyframe.h:57-64)
+    g0 = 0.5 * (bil(t10, t20, t11, t21) - bil(tm0, t00, tm1, t01));
+    g1 = 0.5 * (bil(t01, t11, t02, t12) - bil(t0m, t1m, t00, t10));
+}
+
+// the same for class kClsStraddle: LDS taps, sample_px's weights per sample
+__device__ inline void samples_straddle(const uint8_t* win, const CurWin& cw, double x, double y, double lval,
+                                        double& error, double& g0, double& g1) {
+    auto smp = [&](double sx, double sy) {
+        const int o = ((int)sy - cw.y0) * kCW + ((int)sx - cw.x0);
+        const double d0 = (double)ld_lds_u8(win, o), d1 = (double)ld_lds_u8(win, o + 1);
+        const double d2 = (double)ld_lds_u8(win, o + kCW), d3 = (double)ld_lds_u8(win, o + kCW + 1);
+        const double sxx = sx - floor(sx);
+        const double syy = sy - floor(sy);
+        return double((1 - sxx) * (1 - syy) * d0 + sxx * (1 - syy) * d1 + (1 - sxx) * syy * d2 +
+                      sxx * syy * d3);
+    };
+    error = lval - smp(x, y);
+    g0 = 0.5 * (smp(x + 1, y) - smp(x - 1, y));
+    g1 = 0.5 * (smp(x, y + 1) - smp(x, y - 1));
+}
+
+// and for class kClsSample
+__device__ inline void samples_each(const uint8_t* __restrict__ C, int w, int h, const uint8_t* win,
+                                    const CurWin& cw, double x, double y, double lval, double& error, double& g0,
+                                    double& g1) {
+    error = lval - sample_cw(C, w, h, x, y, win, cw);
+    g0 = 0.5 * (sample_cw(C, w, h, x + 1, y, win, cw) - sample_cw(C, w, h, x - 1, y, win, cw));
+    g1 = 0.5 * (sample_cw(C, w, h, x, y + 1, win, cw) - sample_cw(C, w, h, x, y - 1, win, cw));
+}
+
+// The factored sums (oracle direct_point_partials): J = -g^T Jp with Jp =
+// dPixel/dXi constant over the patch, so sum_p J J^T = Jp^T G Jp and
+// sum_p -e J = Jp^T (sum_p e g) with G = sum_p g g^T: six pixel sums
+// (descending-xor trees, oracle tree_sum_desc64) instead of 28.  jq:
+// point_quotients' result; lane k < 28 gets sum k in *out (*idx = k, -1
+// elsewhere).
+__device__ inline void point_sums_factored(double error, double g0, double g1, double jq, unsigned src_lanes,
+                                           double* out, int* idx) {
+    const int lane = threadIdx.x & 63;
+    PPT(2);
+    const double leaf[6] = {g0 * g0, g0 * g1, g1 * g1, error * g0, error * g1, error * error};
+    const double s = reduce_scatter_6_desc(leaf);
+    PPT(3);
+    // lane k < 28 forms sum k from the six and its four J entries
+    const unsigned sa = src_lanes;
+    const double p0a = bperm_f64(jq, (int)(sa & 0xff)), p1a = bperm_f64(jq, (int)((sa >> 8) & 0xff));
+    const double p0b = bperm_f64(jq, (int)((sa >> 16) & 0xff)), p1b = bperm_f64(jq, (int)(sa >> 24));
+    const double S0 = readlane_f64(s, 0), S1 = readlane_f64(s, 8), S2 = readlane_f64(s, 16);
+    const double S3 = readlane_f64(s, 32), S4 = readlane_f64(s, 40), S5 = readlane_f64(s, 48);
+    double o;
+    if (lane < 21)
+        o = (S0 * (p0a * p0b) + S1 * (p0a * p1b + p1a * p0b)) + S2 * (p1a * p1b);
+    else if (lane < 27)
+        o = S3 * p0a + S4 * p1a;
+    else
+        o = S5;
+    *out = o;
+    *idx = lane < kSums ? lane : -1;
+    PPT(4);
+}
+
+// The per-point scalars a helper wave hands to the point waves of a tile of
+// 9 or 10 points (scalar_pass, below)
+constexpr int kSpHelpers = 2;
+constexpr int kSpPerHelper = 5;
+constexpr int kSpLanes = 12;
+constexpr int kSpPoints = kSpHelpers * kSpPerHelper;
+static_assert(kSpPoints == kWaves - kSpHelpers, "the helpers are the two waves above the tile's points");
+static_assert(kSpPerHelper * kSpLanes <= 64, "a helper's points fit its lanes");
+
+struct SpLds {
+    // per point: [0, 12) the quotients (lane k of the point wave reads k);
+    // [12, 16) w00, w10, w01, w11 (kClsShared) or uc, vc, -, -
+    double v[kSpPoints][16];
+    int cls[kSpPoints][4];  // class, floor(uc), floor(vc), -
+    int ready[kSpPoints];
+};
+
 // The 28 sums of one map point (factored form, oracle direct_point_partials):
 // returns good; lane k < 28 holds sum k in *out (*idx = k, -1 elsewhere).
 // src_lanes: factored_sources() of this lane.
@@ -580,93 +737,57 @@ __device__ inline bool direct_point_rs(const DirectArgs& a, const LevelPair& fp,
     const double hp = 4.0;
     const bool good = r.ok && inside_px(uc - hp, vc - hp, w, h) && inside_px(uc + hp, vc + hp, w, h);
     if (!good) return false;
-    const uint8_t* C = fp.cur;
     const double x = uc + px, y = vc + py;
     double error, g0, g1;
-    // Whole patch in the window (wave-uniform, conservative: every lane's
-    // samples at x, x +- 1 have int() bases in [floor(uc) - 6, floor(uc) + 5],
-    // likewise in y): the five samples read LDS with no per-lane tests;
-    // otherwise sample_cw decides per sample.
     const int fu = (int)floor(uc), fv = (int)floor(vc);
-    if (__builtin_expect(cw.on && fu - 6 >= cw.x0 && fu + 5 <= cw.x0 + kCW - 2 && fv - 6 >= cw.y0 &&
-                             fv + 5 <= cw.y0 + kCW - 2,
-                         1)) {
-        // uc - 6 .. uc + 6 (and vc's) non-negative and in one binade: every
-        // lane's sample coordinate uc + px + {-1, 0, 1} is then exact, its
-        // int() is floor(uc) + px + {-1, 0, 1} and its fraction is exactly
-        // frac(uc), so all five samples of all lanes share one set of bilinear
-        // weights (the same products as the per-sample form) and read 12
-        // distinct taps per lane.  The window's origin is not clamped, so the
-        // window test no longer keeps the coordinates positive: a point with
-        // uc in [4, 5) has gradient samples at uc - 5 in (-1, 0), where
-        // sample_px's int() base is 0 and floor() is -1 (and the fraction is
-        // taken from the negative coordinate), so such a point must take the
-        // per-sample form below.  uc >= 6 (vc >= 6) says so outright; the
-        // shifted compare alone would also refuse it, but only because a
-        // negative uc - 6 carries its sign bit into the shifted word.
-        const bool one_binade = uc >= 6.0 && vc >= 6.0 &&
-                                (__double_as_longlong(uc - 6.0) >> 52) == (__double_as_longlong(uc + 6.0) >> 52) &&
-                                (__double_as_longlong(vc - 6.0) >> 52) == (__double_as_longlong(vc + 6.0) >> 52);
-        if (__builtin_expect(one_binade, 1)) {
+    if (__builtin_expect(patch_in_window(cw.on, cw.x0, cw.y0, fu, fv), 1)) {
+        if (__builtin_expect(patch_one_binade(uc, vc), 1)) {
             const double xx = uc - floor(uc), yy = vc - floor(vc);
             const double w00 = (1 - xx) * (1 - yy), w10 = xx * (1 - yy), w01 = (1 - xx) * yy, w11 = xx * yy;
-            // tap (-1, -1) of this lane: every tap below is a non-negative
-            // immediate offset from it (one address, twelve ds_read_u8)
-            const uint8_t* wb = win + ((fv + py - 1 - cw.y0) * kCW + (fu + px - 1 - cw.x0));
-            auto tap = [&](int dx, int dy) { return (double)ld_lds_u8(wb, (dy + 1) * kCW + (dx + 1)); };
-            const double tm0 = tap(-1, 0), t00 = tap(0, 0), t10 = tap(1, 0), t20 = tap(2, 0);
-            const double tm1 = tap(-1, 1), t01 = tap(0, 1), t11 = tap(1, 1), t21 = tap(2, 1);
-            const double t0m = tap(0, -1), t1m = tap(1, -1), t02 = tap(0, 2), t12 = tap(1, 2);
-            auto bil = [&](double d0, double d1, double d2, double d3) {
-                return double(w00 * d0 + w10 * d1 + w01 * d2 + w11 * d3);
-            };
-            error = r.lval - bil(t00, t10, t01, t11);
-            // GetGradient (include/keyframe.h:57-64)
-            g0 = 0.5 * (bil(t10, t20, t11, t21) - bil(tm0, t00, tm1, t01));
-            g1 = 0.5 * (bil(t01, t11, t02, t12) - bil(t0m, t1m, t00, t10));
+            samples_shared(win, cw, fu, fv, w00, w10, w01, w11, r.lval, error, g0, g1);
         } else {
-            auto smp = [&](double sx, double sy) {
-                const int o = ((int)sy - cw.y0) * kCW + ((int)sx - cw.x0);
-                const double d0 = (double)ld_lds_u8(win, o), d1 = (double)ld_lds_u8(win, o + 1);
-                const double d2 = (double)ld_lds_u8(win, o + kCW), d3 = (double)ld_lds_u8(win, o + kCW + 1);
-                const double sxx = sx - floor(sx);
-                const double syy = sy - floor(sy);
-                return double((1 - sxx) * (1 - syy) * d0 + sxx * (1 - syy) * d1 + (1 - sxx) * syy * d2 +
-                              sxx * syy * d3);
-            };
-            error = r.lval - smp(x, y);
-            g0 = 0.5 * (smp(x + 1, y) - smp(x - 1, y));
-            g1 = 0.5 * (smp(x, y + 1) - smp(x, y - 1));
+            samples_straddle(win, cw, x, y, r.lval, error, g0, g1);
         }
     } else {
-        error = r.lval - sample_cw(C, w, h, x, y, win, cw);
-        g0 = 0.5 * (sample_cw(C, w, h, x + 1, y, win, cw) - sample_cw(C, w, h, x - 1, y, win, cw));
-        g1 = 0.5 * (sample_cw(C, w, h, x, y + 1, win, cw) - sample_cw(C, w, h, x, y - 1, win, cw));
+        samples_each(fp.cur, w, h, win, cw, x, y, r.lval, error, g0, g1);
     }
-    // The factored sums (oracle direct_point_partials): J = -g^T Jp with Jp =
-    // dPixel/dXi constant over the patch, so sum_p J J^T = Jp^T G Jp and
-    // sum_p -e J = Jp^T (sum_p e g) with G = sum_p g g^T: six pixel sums
-    // (descending-xor trees, oracle tree_sum_desc64) instead of 28
-    PPT(2);
-    const double leaf[6] = {g0 * g0, g0 * g1, g1 * g1, error * g0, error * g1, error * error};
-    const double s = reduce_scatter_6_desc(leaf);
-    PPT(3);
-    // lane k < 28 forms sum k from the six and its four J entries
-    const unsigned sa = src_lanes;
-    const double p0a = bperm_f64(jq, (int)(sa & 0xff)), p1a = bperm_f64(jq, (int)((sa >> 8) & 0xff));
-    const double p0b = bperm_f64(jq, (int)((sa >> 16) & 0xff)), p1b = bperm_f64(jq, (int)(sa >> 24));
-    const double S0 = readlane_f64(s, 0), S1 = readlane_f64(s, 8), S2 = readlane_f64(s, 16);
-    const double S3 = readlane_f64(s, 32), S4 = readlane_f64(s, 40), S5 = readlane_f64(s, 48);
-    double o;
-    if (lane < 21)
-        o = (S0 * (p0a * p0b) + S1 * (p0a * p1b + p1a * p0b)) + S2 * (p1a * p1b);
-    else if (lane < 27)
-        o = S3 * p0a + S4 * p1a;
-    else
-        o = S5;
-    *out = o;
-    *idx = lane < kSums ? lane : -1;
-    PPT(4);
+    point_sums_factored(error, g0, g1, jq, src_lanes, out, idx);
+    return true;
+}
+
+// direct_point_rs with the point's scalars (the quotients, the class,
+// floor(uc), floor(vc) and the shared weights or uc, vc) taken from a helper
+// wave's pass over the tile (scalar_pass, below: the same expressions), read
+// once the ready word of point j is up.
+__device__ inline bool direct_point_sp(const DirectArgs& a, const LevelPair& fp, int lv, const RefSample& r,
+                                       const uint8_t* win, const CurWin& cw, const SpLds& sp, int j, double* out,
+                                       int* idx, unsigned src_lanes) {
+    const int lane = threadIdx.x & 63;
+    const int px = (lane >> 3) - 4, py = (lane & 7) - 4;
+    PPT(0);
+    while (__hip_atomic_load(&sp.ready[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+        __builtin_amdgcn_s_sleep(1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const double ql = sp.v[j][lane < 12 ? lane : 11];
+    const double jq = lane < 12 ? ql : 0.0;
+    const double2 s01 = reinterpret_cast<const double2*>(&sp.v[j][12])[0];
+    const double2 s23 = reinterpret_cast<const double2*>(&sp.v[j][12])[1];
+    const int4 ci = *reinterpret_cast<const int4*>(sp.cls[j]);
+    const int cls = __builtin_amdgcn_readfirstlane(ci.x);
+    const int fu = __builtin_amdgcn_readfirstlane(ci.y), fv = __builtin_amdgcn_readfirstlane(ci.z);
+    PPT(1);
+    if (!(r.ok && cls != kClsOut)) return false;
+    double error, g0, g1;
+    if (__builtin_expect(cls == kClsShared, 1)) {
+        samples_shared(win, cw, fu, fv, s01.x, s01.y, s23.x, s23.y, r.lval, error, g0, g1);
+    } else {
+        const double x = s01.x + px, y = s01.y + py;  // uc, vc
+        if (cls == kClsStraddle)
+            samples_straddle(win, cw, x, y, r.lval, error, g0, g1);
+        else
+            samples_each(fp.cur, a.g.w[lv], a.g.h[lv], win, cw, x, y, r.lval, error, g0, g1);
+    }
+    point_sums_factored(error, g0, g1, jq, src_lanes, out, idx);
     return true;
 }
 
@@ -953,6 +1074,58 @@ __device__ inline void merged_ref(const DirectArgs& a, const LevelPair& fp, int 
     }
 }
 
+// ---------------------------------------------------------------- scalar pass
+// A tile of 9 or 10 points on 12 waves leaves waves 10 and 11 without a
+// point.  Much of a point's instruction stream is the same in all 64 lanes
+// of its wave (the quotients, uc and vc, the current-image side of `good`,
+// the window class, the shared bilinear weights), so in such a tile the two
+// idle waves compute it once for every point (helper h = wave - 10: points
+// 5 h .. 5 h + 4, 12 lanes per point, lane 12 p + k = quotient k of point p:
+// one division sequence for 60 quotients) and hand it over in LDS, a ready
+// word per point.  Each value is formed by the expression direct_point_rs
+// forms it with, so a point's sums do not depend on who computed its scalars.
+// The point waves wait within the workgroup for a helper whose work is finite
+// and waits for nothing.
+__device__ inline void scalar_pass(const DirectArgs& a, int lv, const double* cur_pose, const PfLds& pf, int first,
+                                   int T, int helper, SpLds& sp) {
+    const int lane = threadIdx.x & 63;
+    const bool act = lane < kSpPerHelper * kSpLanes;
+    // (the spare lanes repeat the last point's last quotient and store nothing)
+    const int p = act ? lane / kSpLanes : kSpPerHelper - 1;
+    const int k = act ? lane - kSpLanes * p : kSpLanes - 1;
+    const int j = kSpPerHelper * helper + p;
+    const bool valid = act && j < T && first + j < a.n;
+    const double scale = kScale[lv];
+    const int w = a.g.w[lv], h = a.g.h[lv];
+    const double P[3] = {pf.P[j][0], pf.P[j][1], pf.P[j][2]};
+    // (the operands by selects: the helper is alone on its critical path, and
+    // a table would put two LDS round trips on it)
+    const double q = quotient_select(a.K, cur_pose, P, scale, k);
+    const double Q0 = bperm_f64(q, kSpLanes * p), Q1 = bperm_f64(q, kSpLanes * p + 1);
+    const double uc = scale * (Q0 * a.K.fx + a.K.cx);
+    const double vc = scale * (Q1 * a.K.fy + a.K.cy);
+    const double hp = 4.0;
+    const bool in = inside_px(uc - hp, vc - hp, w, h) && inside_px(uc + hp, vc + hp, w, h);
+    const int fu = (int)floor(uc), fv = (int)floor(vc);
+    const bool whole = patch_in_window(pf.cw[j][2] != 0, pf.cw[j][0], pf.cw[j][1], fu, fv);
+    const int cls = !in ? kClsOut : !whole ? kClsSample : patch_one_binade(uc, vc) ? kClsShared : kClsStraddle;
+    const double xx = uc - floor(uc), yy = vc - floor(vc);
+    const double w00 = (1 - xx) * (1 - yy), w10 = xx * (1 - yy), w01 = (1 - xx) * yy, w11 = xx * yy;
+    const bool shared = cls == kClsShared;
+    if (valid) {
+        sp.v[j][k] = q;
+        if (k == 0) {
+            double2* v2 = reinterpret_cast<double2*>(&sp.v[j][12]);
+            v2[0] = make_double2(shared ? w00 : uc, shared ? w10 : vc);
+            v2[1] = make_double2(w01, w11);
+            *reinterpret_cast<int4*>(sp.cls[j]) = make_int4(cls, fu, fv, 0);
+        }
+    }
+    // the point's twelve lanes stored above; then its ready word
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (valid && k == 0) __hip_atomic_store(&sp.ready[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // Tile b of level lv from the prologue's prefetch (the tile phase of
 // direct_level_kernel; direct_tile's arithmetic and tree; FAST: the
 // tolerance-mode point sums).
@@ -970,12 +1143,20 @@ template <bool FAST, bool LV16 = false, int W = kWaves>
 __device__ void direct_tile_pf(const DirectArgs& a, const LevelPair& fp, int lv, const double* cur_pose, int b,
                                const PfLds& pf, bool merged, double* part, int* good, double* s_pts,
                                int* s_good, int* s_cnt = nullptr, double* s_qt = nullptr,
-                               unsigned src_in = kSrcHere) {
+                               unsigned src_in = kSrcHere, SpLds* sp = nullptr) {
     const int wave = wave_id(), lane = threadIdx.x & 63;
     int first, T;
     tile_range(a, b, &first, &T);
     int good_cnt = 0;
     const unsigned src_lanes = FAST ? 0u : src_in != kSrcHere ? src_in : factored_sources();
+    // the scalar pass (sp given: the level kernel's faithful tile phase):
+    // this workgroup's tile leaves exactly the helper waves without a point
+    const bool sp_on = !FAST && W == kWaves && sp && s_cnt && T > kSpPoints - kSpHelpers && T <= kSpPoints;
+    if (sp_on && wave >= kSpPoints) {
+        __builtin_amdgcn_s_setprio(3);
+        scalar_pass(a, lv, cur_pose, pf, first, T, wave - kSpPoints, *sp);
+        __builtin_amdgcn_s_setprio(1);
+    }
     for (int local = wave; local < T; local += W) {
         const int i = first + local;
         double f = 0.0;
@@ -1014,6 +1195,8 @@ __device__ void direct_tile_pf(const DirectArgs& a, const LevelPair& fp, int lv,
                     ok = direct_point_fast(a, fp, lv, cur_pose, r.P, lval, pf.win[local], cw, &ff, &idx);
                 }
                 f = (double)ff;
+            } else if (sp_on) {
+                ok = direct_point_sp(a, fp, lv, r, pf.win[local], cw, *sp, local, &f, &idx, src_lanes);
             } else {
                 ok = direct_point_rs(a, fp, lv, cur_pose, r, pf.win[local], cw, &f, &idx, src_lanes,
                                      s_qt ? s_qt + 12 * wave : nullptr);
@@ -1219,7 +1402,11 @@ __device__ inline void after_solve(const DirectArgs& a, bool merged, SolveLds& L
 // << 16): scalar arguments ahead of the by-value struct are preloaded into
 // SGPRs at wave launch (-amdgpu-kernarg-preload-count, viso_amd/build.py), so
 // the partial loads issue without waiting for a kernel-argument load.
-template <bool FAST>
+// SP: tiles of 9 or 10 points take their per-point scalars from the two idle
+// waves (scalar_pass).  The host launches that form only for a faithful map
+// tiled so (and VISO_DIRECT_SCALAR_PASS not 0), so every other launch runs
+// the kernel without a trace of it.
+template <bool FAST, bool SP = false>
 // (at most 128 VGPRs: four waves per SIMD, the fourth the background's)
 __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double* __restrict__ pre_part,
                                                                  const int* __restrict__ pre_good, int pre_hdr,
@@ -1243,6 +1430,8 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
 #else
     double* const qt = nullptr;
 #endif
+    // the helper waves' per-point scalars of the tile phase (scalar_pass)
+    __shared__ __attribute__((aligned(16))) SpLds s_sp;  // (unreferenced, so not allocated, without SP)
     const int lv = a.level;
     const bool merged = a.merged && lv == kLevels - 1;
     const int prev = lv + 1;
@@ -1281,6 +1470,7 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         if (blockIdx.x < 256) g_pblk[a.probe_seq & (kPRingB - 1)][blockIdx.x][0] = probe_t0;
 #endif
     }
+    if (SP && t >= kThreads - kSpPoints) s_sp.ready[kThreads - 1 - t] = 0;
     lds_barrier();  // the LDS words above; the global loads stay in flight
 
     if (t == 256) {
@@ -1409,7 +1599,8 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
 #pragma unroll
         for (int k = 0; k < 12; ++k) pose[k] = s_pose[k];
         direct_tile_pf<FAST>(a, fp, lv, pose, blockIdx.x, s_pf, merged, a.s.part + (size_t)lv * kMaxTiles * kSums,
-                       a.s.good + lv * kMaxTiles, s_pts, &s_good, &s_cnt, qt, src_lanes);
+                       a.s.good + lv * kMaxTiles, s_pts, &s_good, &s_cnt, qt, src_lanes,
+                       SP ? &s_sp : nullptr);
     }
 #ifdef VISO_PROBE
     // block 0 exit: its stamps to the launch's ring slot.  The exit stamp is
@@ -1949,7 +2140,7 @@ void launch_direct_levels(const FrameDev& last_pyr, const FrameDev& cur_pyr, con
                           const double K[4], const double* points, int n,
                           const double* pose_last12, const double* pose_seed12,
                           const DirectScratch& s, double* stats, const DirectPrev* merge,
-                          hipStream_t stream, int precision, bool bg) {
+                          hipStream_t stream, int precision, bool bg, bool scalar_pass) {
     DirectArgs a = direct_args(last_pyr, cur_pyr, g, K, points, n, pose_last12, pose_seed12, s,
                                stats, precision == VISO_PRECISION_FAST);
     if (merge) {
@@ -1976,6 +2167,8 @@ void launch_direct_levels(const FrameDev& last_pyr, const FrameDev& cur_pyr, con
         const int hdr = a.n_tiles | (solve ? 1 << 16 : 0) | (bg ? kHdrBg : 0);
         if (precision == VISO_PRECISION_FAST)
             direct_level_kernel<true><<<grid, kThreads, 0, stream>>>(pp, pg, hdr, a);
+        else if (scalar_pass && a.tile > kSpPoints - kSpHelpers && a.tile <= kSpPoints)
+            direct_level_kernel<false, true><<<grid, kThreads, 0, stream>>>(pp, pg, hdr, a);
         else
             direct_level_kernel<false><<<grid, kThreads, 0, stream>>>(pp, pg, hdr, a);
         a.merged = 0;
@@ -2118,9 +2311,9 @@ void launch_direct_pose(const FrameDev& last_pyr, const FrameDev& cur_pyr, const
                         const double K[4], const double* points, int n,
                         const double* pose_last12, const double* pose_seed12,
                         const DirectScratch& s, double* stats, double* pose_out, double* log,
-                        int log_index, hipStream_t stream, int precision) {
+                        int log_index, hipStream_t stream, int precision, bool scalar_pass) {
     launch_direct_levels(last_pyr, cur_pyr, g, K, points, n, pose_last12, pose_seed12, s, stats,
-                         nullptr, stream, precision);
+                         nullptr, stream, precision, false, scalar_pass);
     launch_direct_final(last_pyr, cur_pyr, g, K, points, n, pose_last12, s, stats, pose_out, log,
                         log_index, stream, precision);
 }

@@ -1392,7 +1392,7 @@ int viso_ctx::on_new_frame(int cur) {
                 launch_direct_levels(frame(last_slot), frame(cur), g, K, (const double*)map_pts.ptr,
                                      n_map, pose_of(last_slot), pose_of(last_slot), direct,
                                      (double*)direct_stats.ptr, dpend ? &m : nullptr, stream, p.precision,
-                                     bg_active);
+                                     bg_active, direct_scalar_pass);
                 dev_tl.mark(frames, 4, stream);
             }
             if (dpend) {

@@ -317,12 +317,15 @@ void launch_direct_pose(const FrameDev& last, const FrameDev& cur, const PyrGeom
                         const double K[4], const double* points, int n,
                         const double* pose_last12, const double* pose_seed12,
                         const DirectScratch& s, double* stats, double* pose_out, double* log,
-                        int log_index, hipStream_t stream, int precision = VISO_PRECISION_FAITHFUL);
+                        int log_index, hipStream_t stream, int precision = VISO_PRECISION_FAITHFUL,
+                        bool scalar_pass = true);
 // The same call split for the frame pipeline: L(3..0) of this frame, then F
 // later.  With `merge`, L(3) also runs the previous frame's pending F (its
 // level-0 solve; the solved pose is this frame's `last` pose and seed, so
 // pose_last12 / pose_seed12 are read only by L(2..0), after L(3) wrote them
 // to merge->pose_out).
+// scalar_pass: faithful tiles of 9 or 10 points take their per-point scalars
+// from the workgroup's two idle waves (direct.hip scalar_pass; same bits).
 struct DirectPrev {
     FrameDev last, cur;         // the previous frame's pair (rare continuation)
     const double* pose_last12;  // its `last` pose
@@ -340,7 +343,8 @@ void launch_direct_levels(const FrameDev& last, const FrameDev& cur, const PyrGe
                           const double K[4], const double* points, int n,
                           const double* pose_last12, const double* pose_seed12,
                           const DirectScratch& s, double* stats, const DirectPrev* merge,
-                          hipStream_t stream, int precision = VISO_PRECISION_FAITHFUL, bool bg = false);
+                          hipStream_t stream, int precision = VISO_PRECISION_FAITHFUL, bool bg = false,
+                          bool scalar_pass = true);
 void launch_direct_final(const FrameDev& last, const FrameDev& cur, const PyrGeom& g,
                          const double K[4], const double* points, int n,
                          const double* pose_last12, const DirectScratch& s, double* stats,
