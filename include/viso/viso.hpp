@@ -378,6 +378,35 @@ public:
         return out;
     }
 
+    // Point refinement (viso_set_point_refine): every tracking frame's final
+    // pose and LK-aligned positions go into a ring of `window` frames; every
+    // interval-th tracking frame each map point's depth along its anchor
+    // keyframe's ray is refined on them.  0 = off.
+    void SetPointRefine(int interval, int window = 5, int iterations = 3, double huber_px = 1.0,
+                        double max_shift_px = 8.0, int min_obs = 3, double max_rel_sigma = 0.05) {
+        check(viso_set_point_refine(ctx_, interval, window, iterations, huber_px, max_shift_px, min_obs,
+                                    max_rel_sigma),
+              "viso_set_point_refine");
+    }
+    // viso_get_point_refine's info[8]
+    std::array<int64_t, 8> PointRefine() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_point_refine(ctx_, info.data()), "viso_get_point_refine");
+        return info;
+    }
+    // the last refinement's {status, steps} per point (empty before the first)
+    std::vector<std::array<uint8_t, 2>> PointRefineStatus() const {
+        size_t n = 0;
+        check(viso_get_point_refine_status(ctx_, nullptr, nullptr, 0, &n), "viso_get_point_refine_status");
+        std::vector<uint8_t> status(n), steps(n);
+        if (n)
+            check(viso_get_point_refine_status(ctx_, status.data(), steps.data(), n, &n),
+                  "viso_get_point_refine_status");
+        std::vector<std::array<uint8_t, 2>> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = {status[i], steps[i]};
+        return out;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

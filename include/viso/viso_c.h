@@ -186,7 +186,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_MAPWIN 9 /* one retirement of the sliding-window map (viso_set_map_window) */
 #define VISO_KERNEL_REFINE 10 /* one frame's pose refinement (viso_set_pose_refine) */
 #define VISO_KERNEL_CULL 11 /* the record update and cull launches (viso_set_point_cull) */
-#define VISO_KERNEL_COUNT 12
+#define VISO_KERNEL_POINTS 12 /* the record and refine launches (viso_set_point_refine) */
+#define VISO_KERNEL_COUNT 13
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -465,6 +466,77 @@ int viso_point_tracks_update(viso_ctx* ctx, const double* points, const int32_t*
 int viso_points_cull(viso_ctx* ctx, const double* points, const int32_t* host, const int32_t* tracks4, int32_t n,
                      int32_t max_fail_run, int32_t min_points, double* out_points, int32_t* out_host,
                      int32_t* out_tracks4, uint8_t* keep, size_t* n_out, int32_t counts[4]);
+
+/* Point refinement (the repo's own spec, restated in
+ * tests/point_refine_ref.py; DESIGN.md §Point refinement): the structure half
+ * of the "pose and structure refinement" on the LK-aligned positions, which
+ * the reference only draws.  A point's LK template is its anchor keyframe's
+ * patch at the point's projection there, so the aligned positions measure the
+ * depth along the ray from the anchor's centre C through the point: the
+ * refinement moves P along that ray and nothing else (its projection in the
+ * anchor, the templates and its identity stay).
+ *  - Record, once per tracking frame, behind the frame's LK alignment, its pose
+ *    refinement and its track update, with the frame's final pose (as
+ *    viso_get_poses) and its LK row (as viso_get_alignment), into slot
+ *    count % window of an observation ring, count + 1: point i is flagged when
+ *    pair_kf >= 0, success != 0 and |uv_after - uv_before|^2 <= max_shift_px^2;
+ *    the stored uv is uv_after.  count = 0 whenever the LK templates are
+ *    rebuilt (map creation, an insertion, a retirement, an applied cull) and
+ *    when the mode is switched on (or its window changed); the live slots are
+ *    the first min(count, window).
+ *  - Refinement, on every interval-th tracking frame right behind its record,
+ *    ahead of the cull and the insertion check, per point: a = the template's
+ *    keyframe; a < 0 -> status 5.  Fewer than min_obs flagged live slots ->
+ *    status 1.  Pass k = 0..iterations at P_k (P_0 = P), D = P_k - C: per
+ *    flagged live slot with Pc = R_s P_k + t_s, Pc.z > 0: r = uv - projection,
+ *    e = |r|, the Huber weight and rho of viso_set_pose_refine, g = the
+ *    projection's derivative along -D; H = sum w g.g, b = sum w g.r, cost =
+ *    sum rho, each the pairwise tree over slots 0..7.  In this order: k = 0 and
+ *    fewer than min_obs slots used -> status 1; k = 0 and H max_rel_sigma^2 < 1
+ *    (a 1 px error moves the depth by more than max_rel_sigma, relative) ->
+ *    status 4; k >= 1 and cost_k >= cost_{k-1} -> P_{k-1}, status 3;
+ *    k = iterations -> P_k, status 0; delta = b / H not finite or 1 + delta
+ *    outside (0.5, 2) -> P_k, status 2; else P_{k+1} = C + D / (1 + delta).
+ * The cull, the insertion check, the BA and the next frame see the refined
+ * points; no template rebuild follows.  Two more launches on a refinement
+ * frame, one on the others, no host synchronisation; the frame's LK alignment
+ * runs at once on the context stream (no background or batched alignment while
+ * it is on).  fp64 in both precision modes.  interval 0 (default) = off.
+ * VISO_ERR_ARG unless interval == 0, or interval >= 1, 2 <= window <= 8,
+ * 1 <= iterations <= 10, huber_px > 0, max_shift_px > 0, 1 <= min_obs <=
+ * window, 0 < max_rel_sigma <= 1, all finite.  May be set while tracking: the
+ * next frame sees it. */
+int viso_set_point_refine(viso_ctx* ctx, int32_t interval, int32_t window, int32_t iterations, double huber_px,
+                          double max_shift_px, int32_t min_obs, double max_rel_sigma);
+/* info = {interval, window, refinements run, points moved in all, and of the
+ * last refinement: the number of frames processed before its frame (-1: none
+ * yet), its eligible points (an anchor and min_obs flagged slots), the points
+ * it moved (steps >= 1), its status-4 points}. */
+int viso_get_point_refine(viso_ctx* ctx, int64_t info[8]);
+/* The last refinement's status and kept steps per point (of the map it ran
+ * on): the first min(cap, points) are written; *n = that map's point count (0:
+ * no refinement yet).  VISO_ERR_STATE when the mode is off. */
+int viso_get_point_refine_status(viso_ctx* ctx, uint8_t* status, uint8_t* steps, size_t cap, size_t* n);
+/* Stage entry (parity tests): one frame's record on host data, by the launch
+ * of the frame path.  The LK row (n, 0..16384; uv n x 2); valid_out: n flags;
+ * uv_out: n x 2.  VISO_ERR_ARG on any out-of-range or NULL argument. */
+int viso_point_obs_record(viso_ctx* ctx, const int32_t* pair_kf, const uint8_t* success, const double* uv_before,
+                          const double* uv_after, int32_t n, double max_shift_px, uint8_t* valid_out,
+                          double* uv_out);
+/* Stage entry (parity tests): one refinement on host data, by the launch of
+ * the frame path, with the context's intrinsics.  points: n x 3 world
+ * (0..16384); anchor_kf: n keyframe indices (< n_kf; < 0: none); kf_poses:
+ * n_kf x 12 (1..8); frame_poses: m x 12, the live slots (1..8); obs_valid:
+ * m x n; obs_uv: m x n x 2; 1 <= iterations <= 10, huber_px > 0,
+ * 1 <= min_obs <= 8, 0 < max_rel_sigma <= 1.  Outputs: out_points (n x 3),
+ * status, steps (n each), costs (n x 2: cost_0 and the cost at the result; 0
+ * where no pass ran), counts = {eligible, moved, status 4, status 2}.
+ * VISO_ERR_ARG on any out-of-range or NULL argument. */
+int viso_points_refine(viso_ctx* ctx, const double* points, const int32_t* anchor_kf, int32_t n,
+                       const double* kf_poses, int32_t n_kf, const double* frame_poses, int32_t m,
+                       const uint8_t* obs_valid, const double* obs_uv, int32_t iterations, double huber_px,
+                       int32_t min_obs, double max_rel_sigma, double* out_points, uint8_t* status, uint8_t* steps,
+                       double* costs, int32_t counts[4]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

@@ -277,6 +277,52 @@ class Context:
         return {"points": out[:m.value].copy(), "host": oh[:m.value].copy(), "tracks": ot[:m.value].copy(),
                 "keep": keep[:n].copy(), "n": int(m.value), "counts": [int(c) for c in counts]}
 
+    def point_obs_record(self, pair_kf, success, uv_before, uv_after, max_shift_px: float = 8.0):
+        """viso_point_obs_record: one frame's record into the observation ring
+        (viso_set_point_refine) on host data: the LK row as ``lk_align``
+        returns it.  Returns (valid (n,) uint8, uv (n, 2))."""
+        pk = np.ascontiguousarray(pair_kf, dtype=np.int32).reshape(-1)
+        n = pk.shape[0]
+        sc = np.ascontiguousarray(success, dtype=np.uint8).reshape(-1)
+        ub = np.ascontiguousarray(uv_before, dtype=np.float64).reshape(-1, 2)
+        ua = np.ascontiguousarray(uv_after, dtype=np.float64).reshape(-1, 2)
+        if not (sc.shape[0] == ub.shape[0] == ua.shape[0] == n):
+            raise ValueError("point_obs_record: one LK entry per point")
+        valid = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float64)
+        _lib.call("viso_point_obs_record", self.h, _p(pk), _p(sc), _p(ub), _p(ua), n, float(max_shift_px),
+                  _p(valid), _p(uv))
+        return valid[:n].copy(), uv[:n].copy()
+
+    def refine_points(self, points, anchor_kf, kf_poses, frame_poses, obs_valid, obs_uv, iterations: int = 3,
+                      huber_px: float = 1.0, min_obs: int = 3, max_rel_sigma: float = 0.05):
+        """viso_points_refine: one point refinement (viso_set_point_refine) on
+        host data with the context's intrinsics: points (n, 3) world,
+        anchor_kf (n,) keyframe indices (< 0: none), kf_poses (k, 12),
+        frame_poses (m, 12) the live ring slots, obs_valid (m, n), obs_uv
+        (m, n, 2).  Returns dict(points (n, 3), status (n,), steps (n,), costs
+        (n, 2), counts [eligible, moved, status 4, status 2])."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        an = np.ascontiguousarray(anchor_kf, dtype=np.int32).reshape(-1)
+        kp = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        fp = np.ascontiguousarray(frame_poses, dtype=np.float64).reshape(-1, 12)
+        m = fp.shape[0]
+        ov = np.ascontiguousarray(obs_valid, dtype=np.uint8).reshape(m, -1)
+        uv = np.ascontiguousarray(obs_uv, dtype=np.float64).reshape(m, -1, 2)
+        if not (an.shape[0] == ov.shape[1] == uv.shape[1] == n):
+            raise ValueError("refine_points: one anchor and m observations per point")
+        out = np.zeros((max(n, 1), 3), np.float64)
+        status = np.zeros(max(n, 1), np.uint8)
+        steps = np.zeros(max(n, 1), np.uint8)
+        costs = np.zeros((max(n, 1), 2), np.float64)
+        counts = np.zeros(4, np.int32)
+        _lib.call("viso_points_refine", self.h, _p(pts), _p(an), n, _p(kp), kp.shape[0], _p(fp), m, _p(ov), _p(uv),
+                  int(iterations), float(huber_px), int(min_obs), float(max_rel_sigma), _p(out), _p(status),
+                  _p(steps), _p(costs), _p(counts))
+        return {"points": out[:n].copy(), "status": status[:n].copy(), "steps": steps[:n].copy(),
+                "costs": costs[:n].copy(), "counts": [int(c) for c in counts]}
+
     # ------------------------------------------------------------ timing
     def photometric_ba(self, kf_images, kf_poses, points, host, iterations: int = 5):
         """viso_photometric_ba: the BA of include/bundle_adjuster.h:22-106 on
@@ -341,6 +387,21 @@ def cull_points(points, host, tracks, max_fail_run=3, min_points=50, width=640, 
                 device: int = 0):
     """``Context.cull_points`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).cull_points(points, host, tracks, max_fail_run, min_points)
+
+
+def point_obs_record(pair_kf, success, uv_before, uv_after, max_shift_px=8.0, width=640, height=480, K=None,
+                     device: int = 0):
+    """``Context.point_obs_record`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).point_obs_record(pair_kf, success, uv_before, uv_after,
+                                                                     max_shift_px)
+
+
+def refine_points(points, anchor_kf, kf_poses, frame_poses, obs_valid, obs_uv, iterations=3, huber_px=1.0,
+                  min_obs=3, max_rel_sigma=0.05, width=640, height=480, K=None, device: int = 0):
+    """``Context.refine_points`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).refine_points(points, anchor_kf, kf_poses, frame_poses,
+                                                                  obs_valid, obs_uv, iterations, huber_px, min_obs,
+                                                                  max_rel_sigma)
 
 
 def default_context(width: int = 640, height: int = 480, device: int = 0, K=None) -> Context:

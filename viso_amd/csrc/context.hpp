@@ -388,6 +388,22 @@ struct viso_ctx {
     int tracks_zero(int first, int count);
     int update_tracks(int cur);
     int cull_points();
+    // point refinement (viso_set_point_refine; pointrefine.hip): every
+    // tracking frame's final pose and LK row go into a ring of
+    // prefine_window slots (the frame is finished inside on_new_frame, as
+    // for the pose refinement); every prefine_interval-th tracking frame each
+    // map point's depth along its anchor keyframe's ray is refined on the
+    // ring's observations, in place.  0 = off (prefine_buf null).
+    // prefine_count: frames recorded since the ring was last emptied
+    // (build_lk_templates, the mode switched on)
+    int prefine_interval = 0, prefine_window = 0, prefine_iterations = 0, prefine_min_obs = 0;
+    double prefine_huber = 0.0, prefine_max_shift = 0.0, prefine_sigma = 0.0;
+    int64_t prefine_count = 0, prefine_runs = 0, prefine_last_frame = -1;
+    int prefine_last_n = 0;  // the points of the last refinement
+    viso::DevBuf prefine_buf;  // counters, the ring, the last refinement's status / steps / costs
+    bool prefine_on() const { return prefine_interval > 0; }
+    int record_obs(int cur);
+    int refine_points();
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

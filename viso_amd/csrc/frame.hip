@@ -229,7 +229,7 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf};
+                      &pt_tracks, &cull_buf, &prefine_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -648,9 +648,10 @@ int viso_ctx::host_lk_batch() const {
 
 int viso_ctx::finish_host_call() {
     // outside tracking, and with keyframe insertion (its decision reads the
-    // frame's nGood at once), pose refinement or point culling (every frame
-    // is finished inside on_new_frame), as every other call
-    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || bg_active)
+    // frame's nGood at once), pose refinement, point culling or point
+    // refinement (every frame is finished inside on_new_frame), as every
+    // other call
+    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || bg_active)
         return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
@@ -682,8 +683,8 @@ bool viso_ctx::host_queue_eligible() {
         const char* e = getenv("VISO_HOST_CHUNK");
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
-    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && bg_on() &&
-           direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
+    return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
+           bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
@@ -804,8 +805,8 @@ int viso_ctx::stage_poses() {
 // frame of such a chunk is a tracking frame, so every ready flag is raised:
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
-                                      lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !dpend &&
-                                      lk_pending.empty(); }
+                                      lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
+                                      !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1022,6 +1023,9 @@ int viso_ctx::build_lk_templates() {
     if (!rc) rc = lk_tmpl_uv.ensure(m * 16);
     if (rc) return rc;
     launch_lk_template(lk_args(), stream);
+    // the anchors and the point indexing change here: the observation ring
+    // of the point refinement (pointrefine.hip) starts again
+    prefine_count = 0;
     return VISO_OK;
 }
 
@@ -1425,19 +1429,29 @@ int viso_ctx::on_new_frame(int cur) {
             // pose refinement (viso_set_pose_refine, refine.hip): this frame's
             // final solve and its LK alignment now, then the refine launch on
             // that LK row; everything below and the next frame see its pose
-            if ((refine_on() || cull_on()) && n_map > 0) {
+            if ((refine_on() || cull_on() || prefine_on()) && n_map > 0) {
                 int rc = finish_call(stream);
                 if (!rc && refine_on()) rc = refine_frame(cur);
                 // map point culling (viso_set_point_cull, pointcull.hip):
                 // every point's track record on this frame's LK row at its
                 // final pose
                 if (!rc && cull_on()) rc = update_tracks(cur);
+                // point refinement (viso_set_point_refine, pointrefine.hip):
+                // the frame's final pose and LK row into the observation ring
+                if (!rc && prefine_on()) rc = record_obs(cur);
                 if (rc) return rc;
             }
             // keyframe insertion (stereo: oracle_viso.cpp; monocular:
             // monokf.hip): every interval-th tracking frame, one host sync
             // for its nGood
             ++track_cnt;
+            // every prefine_interval-th tracking frame every point's depth
+            // along its anchor's ray is refined on the ring, ahead of the
+            // cull and the insertion check (no host sync)
+            if (prefine_on() && n_map > 0 && track_cnt % prefine_interval == 0) {
+                const int rc = refine_points();
+                if (rc) return rc;
+            }
             // every cull_interval-th tracking frame the points that kept
             // failing leave the map, ahead of the insertion check (one host
             // sync)

@@ -291,6 +291,47 @@ size_t point_cull_scratch_at(PointCullArgs& a, void* base, int n);
 void launch_point_tracks(const PointCullArgs& a, hipStream_t stream);
 void launch_point_cull(const PointCullArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- point refinement
+// The observation ring's record and one refinement of viso_set_point_refine
+// (pointrefine.hip): everything in device memory.  Slot s of the ring holds a
+// frame's pose at poses + 12 s and, for point i, a flag at valid[s stride + i]
+// and uv at uv[2 (s stride + i)].
+constexpr int kMaxObsSlots = 8;
+struct PointObsArgs {
+    int n;
+    const int32_t* pair_kf;   // the frame's LK row: n each (uv: n x 2)
+    const uint8_t* success;
+    const double* uv_before;
+    const double* uv_after;
+    double max_shift;         // pixels
+    const double* pose;       // 12, Tcw (null: no pose is stored)
+    uint8_t* valid_out;       // the slot's n flags and n x 2 uv
+    double* uv_out;
+    double* pose_out;         // the slot's 12 doubles
+};
+struct PointRefineArgs {
+    double K[4];              // fx, fy, cx, cy
+    double* pts;              // n x 3 (world), refined in place
+    int n;
+    const int32_t* anchor_kf; // n: the LK template's keyframe (< 0: none)
+    const double* kf_poses;   // n_kf x 12
+    int n_kf;
+    const double* poses;      // m x 12: the live slots' poses
+    const uint8_t* valid;     // m x stride
+    const double* uv;         // m x stride x 2
+    size_t stride;
+    int m;                    // live slots, 1..kMaxObsSlots
+    int iterations, min_obs;
+    double huber, max_rel_sigma;
+    uint8_t* status;          // n each
+    uint8_t* steps;
+    double* costs;            // n x 2: cost_0, the cost at the result (0: no pass ran)
+    int* counts;              // {eligible, moved, status 4, status 2}; zero before the launch
+    unsigned long long* moved_total;  // += moved (null: not kept)
+};
+void launch_point_obs(const PointObsArgs& a, hipStream_t stream);
+void launch_point_refine(const PointRefineArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

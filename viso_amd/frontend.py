@@ -199,6 +199,38 @@ class Viso(FrameHandler):
             _lib.call("viso_get_point_tracks", self.ctx.h, out.ctypes.data, n.value, ctypes.byref(n))
         return out
 
+    def set_point_refine(self, interval: int, window: int = 5, iterations: int = 3, huber_px: float = 1.0,
+                         max_shift_px: float = 8.0, min_obs: int = 3, max_rel_sigma: float = 0.05) -> None:
+        """Point refinement (viso_set_point_refine): every tracking frame's
+        final pose and LK-aligned positions go into a ring of `window` frames;
+        every `interval`-th tracking frame each map point's depth along its
+        anchor keyframe's ray is refined on them, `iterations` Huber-weighted
+        Gauss-Newton steps at most, when at least `min_obs` frames observe it
+        and a pixel of error moves the depth by at most `max_rel_sigma`,
+        relative.  interval 0 = off."""
+        _lib.call("viso_set_point_refine", self.ctx.h, int(interval), int(window), int(iterations), float(huber_px),
+                  float(max_shift_px), int(min_obs), float(max_rel_sigma))
+
+    def point_refine(self) -> np.ndarray:
+        """viso_get_point_refine: int64[8] = interval, window, refinements
+        run, points moved in all, then of the last refinement: frames
+        processed before its frame (-1: none yet), its eligible points, the
+        points it moved, its status-4 points."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_point_refine", self.ctx.h, info.ctypes.data)
+        return info
+
+    def point_refine_status(self):
+        """The last refinement's (status, steps) per point, uint8 each
+        (viso_get_point_refine_status); empty before the first refinement."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_point_refine_status", self.ctx.h, None, None, 0, ctypes.byref(n))
+        status, steps = np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint8)
+        if n.value:
+            _lib.call("viso_get_point_refine_status", self.ctx.h, status.ctypes.data, steps.ctypes.data, n.value,
+                      ctypes.byref(n))
+        return status, steps
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
