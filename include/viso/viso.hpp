@@ -407,6 +407,35 @@ public:
         return out;
     }
 
+    // Warped LK alignment (viso_set_lk_warp): every keyframe patch is warped
+    // into the current view by the affine map its point's depth and the two
+    // poses imply and taken from the pyramid level that matches its scale.
+    // mode 0 = off.
+    void SetLkWarp(int mode, double max_area_ratio = 64.0) {
+        check(viso_set_lk_warp(ctx_, mode, max_area_ratio), "viso_set_lk_warp");
+    }
+    // viso_get_lk_warp's info[8]
+    std::array<int64_t, 8> LkWarp() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_lk_warp(ctx_, info.data()), "viso_get_lk_warp");
+        return info;
+    }
+    // the last frame's warp rows: A (4 per point), shift, status
+    struct LkWarpRows {
+        std::vector<double> A;
+        std::vector<int8_t> shift;
+        std::vector<uint8_t> status;
+    };
+    LkWarpRows LkWarpRowsLast() const {
+        size_t n = 0;
+        check(viso_get_lk_warp_rows(ctx_, nullptr, nullptr, nullptr, 0, &n), "viso_get_lk_warp_rows");
+        LkWarpRows r{std::vector<double>(4 * n), std::vector<int8_t>(n), std::vector<uint8_t>(n)};
+        if (n)
+            check(viso_get_lk_warp_rows(ctx_, r.A.data(), r.shift.data(), r.status.data(), n, &n),
+                  "viso_get_lk_warp_rows");
+        return r;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

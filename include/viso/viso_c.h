@@ -187,7 +187,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_REFINE 10 /* one frame's pose refinement (viso_set_pose_refine) */
 #define VISO_KERNEL_CULL 11 /* the record update and cull launches (viso_set_point_cull) */
 #define VISO_KERNEL_POINTS 12 /* the record and refine launches (viso_set_point_refine) */
-#define VISO_KERNEL_COUNT 13
+#define VISO_KERNEL_LKWARP 13 /* a batched launch of the warped LK alignment (viso_set_lk_warp) */
+#define VISO_KERNEL_COUNT 14
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -537,6 +538,46 @@ int viso_points_refine(viso_ctx* ctx, const double* points, const int32_t* ancho
                        const uint8_t* obs_valid, const double* obs_uv, int32_t iterations, double huber_px,
                        int32_t min_obs, double max_rel_sigma, double* out_points, uint8_t* status, uint8_t* steps,
                        double* costs, int32_t counts[4]);
+
+/* Warped LK alignment (the repo's own spec; no reference
+ * counterpart).  LKAlignment's template is the unwarped 8x8 patch of the
+ * point's anchor keyframe at the current image's pyramid level, which stops
+ * being found as the patch's scale or orientation changes.  With mode 1 every
+ * tracking frame's alignment first forms, per map point, the affine map A
+ * (anchor level 0 -> current level 0) that the point's depth in the anchor
+ * and the two poses imply (finite differences of 4 px on the plane z = depth
+ * of the anchor camera), takes the template of every level through A^-1 from
+ * the pyramid level r = l + shift of the anchor that matches its scale
+ * (|det A| > 3: one level coarser per factor 4; < 1/3: finer), and then runs
+ * LKAlignmentSingle's iterations unchanged, the bounds test on the current
+ * coordinates.  A warp whose area ratio |det A| is outside
+ * [1 / max_area_ratio, max_area_ratio], that is not finite, or whose plane
+ * points are not in front of both cameras is rejected: the point counts as
+ * paired and not aligned, uv_after = uv_before.  A level whose template taps
+ * leave the reference level is skipped.  fp64 in both precision modes.
+ * mode 0 = off (default): nothing changes.  mode: 0 or 1; max_area_ratio in
+ * [4, 64] (64 suggested); anything else VISO_ERR_ARG.  May be called while
+ * tracking (pending work is settled first).  While on, LK alignment runs as
+ * batched launches of the warped kernel (VISO_KERNEL_LKWARP) instead of the
+ * chunk-resident grid. */
+int viso_set_lk_warp(viso_ctx* ctx, int32_t mode, double max_area_ratio);
+/* info = {mode, frames aligned with the mode on, then of the last frame's row:
+ * points paired, aligned (success), rejected warps (status 2), points with
+ * shift < 0, with shift > 0, skipped levels summed over the points}. */
+int viso_get_lk_warp(viso_ctx* ctx, int64_t info[8]);
+/* The last frame's warp rows, as viso_get_alignment returns its LK row: A4
+ * (n x 4: A00, A01, A10, A11), shift (n), status (n): 0 aligned through the
+ * warp, 1 not paired (out of view or no keyframe), 2 warp rejected; bits 4-6
+ * the number of skipped levels.  The first min(cap, n) are written; *n = the
+ * row's points.  VISO_ERR_STATE while the mode is off. */
+int viso_get_lk_warp_rows(viso_ctx* ctx, double* A4, int8_t* shift, uint8_t* status, size_t cap, size_t* n);
+/* Stage entry (parity tests): viso_lk_align's arguments and outputs by the
+ * warped kernel, plus max_area_ratio and the three warp outputs. */
+int viso_lk_align_warped(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                         const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                         const double* points, int32_t n_points, double max_area_ratio, int32_t* pair_kf,
+                         uint8_t* success, double* uv_before, double* uv_after, double* A4, int8_t* shift,
+                         uint8_t* status);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

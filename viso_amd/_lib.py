@@ -19,7 +19,7 @@ ERRORS = {-1: "VISO_ERR_ARG", -2: "VISO_ERR_HIP", -3: "VISO_ERR_CAPACITY",
 STATE_INITIALIZATION, STATE_RUNNING, STATE_FINISHED = 0, 1, 2
 KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "direct": 5,
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
-              "points": 12}
+              "points": 12, "lkwarp": 13}
 
 
 class VisoError(RuntimeError):
@@ -106,6 +106,11 @@ SIGNATURES = {
     "viso_point_obs_record": [_vp, _vp, _vp, _vp, _vp, _i32, _d, _vp, _vp],
     "viso_points_refine": [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _d, _i32, _d, _vp, _vp, _vp,
                            _vp, _vp],
+    "viso_set_lk_warp": [_vp, _i32, _d],
+    "viso_get_lk_warp": [_vp, _vp],
+    "viso_get_lk_warp_rows": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "viso_lk_align_warped": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _d, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp],
     "viso_version": [],
     # north-star stereo VO (include/viso/viso_svo.h)
     "viso_svo_default_params": [_vp, _i32, _i32, _d, _d, _d, _d, _d],

@@ -132,6 +132,29 @@ class Context:
                   _p(sc), _p(ub), _p(ua))
         return pk, sc, ub, ua
 
+    def lk_align_warped(self, kf_pyrs, kf_poses, cur_pyr, cur_pose, width, height, points,
+                        max_area_ratio: float = 64.0):
+        """viso_lk_align_warped: ``lk_align`` by the warped kernel
+        (viso_set_lk_warp).  Returns (pair_kf, success, uv_before, uv_after,
+        A (n, 4), shift (n,) int8, status (n,) uint8)."""
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple))
+                                   else kf_pyrs, dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        pk = np.zeros(n, np.int32)
+        sc = np.zeros(n, np.uint8)
+        ub = np.zeros((n, 2), np.float64)
+        ua = np.zeros((n, 2), np.float64)
+        A = np.zeros((n, 4), np.float64)
+        sh = np.zeros(n, np.int8)
+        st = np.zeros(n, np.uint8)
+        cp = np.ascontiguousarray(cur_pose, dtype=np.float64).reshape(12)
+        _lib.call("viso_lk_align_warped", self.h, _p(kfp), _p(kposes), kposes.shape[0],
+                  _p(np.ascontiguousarray(cur_pyr)), _p(cp), width, height, _p(pts), n, float(max_area_ratio),
+                  _p(pk), _p(sc), _p(ub), _p(ua), _p(A), _p(sh), _p(st))
+        return pk, sc, ub, ua, A, sh, st
+
     def pose_2d2d(self, p1: np.ndarray, p2: np.ndarray, R0=None, T0=None):
         """PoseEstimation2d2d + SelectMotion (src/viso.cpp:178-256, 520-638) on
         normalised (n,3) points.  Returns dict(R, T, inliers, points3d,

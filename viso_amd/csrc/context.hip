@@ -336,16 +336,21 @@ int viso_direct_pose(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_py
     return VISO_OK;
 }
 
-int viso_lk_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
-                  const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
-                  const double* points, int32_t n, int32_t* pair_kf, uint8_t* success,
-                  double* uv_before, double* uv_after) {
+// viso_lk_align (warp == false) and viso_lk_align_warped: the same staging,
+// the batched kernel or the warped one
+static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                          const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                          const double* points, int32_t n, int32_t* pair_kf, uint8_t* success,
+                          double* uv_before, double* uv_after, bool warp, double max_area_ratio, double* A4,
+                          int8_t* shift, uint8_t* status) {
     if (!c || !kf_pyrs || !kf_poses || n_kf <= 0 || n_kf > kMaxKeyframes || !cur_pyr || !cur_pose ||
         n < 0)
         return VISO_ERR_ARG;
+    if (warp && !(max_area_ratio >= 4.0 && max_area_ratio <= 64.0)) return VISO_ERR_ARG;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     if (n == 0) return VISO_OK;
     if (!points || !pair_kf || !success || !uv_before || !uv_after) return VISO_ERR_ARG;
+    if (warp && (!A4 || !shift || !status)) return VISO_ERR_ARG;
     VISO_HIP_CHECK(hipSetDevice(c->device));
     PyrGeom g = make_geom(width, height);
     Bump b;
@@ -353,6 +358,8 @@ int viso_lk_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, i
            o_c = b.take(g.bytes), o_cp = b.take(96), o_p = b.take(24 * (size_t)n),
            o_pk = b.take(4 * (size_t)n), o_s = b.take((size_t)n), o_ub = b.take(16 * (size_t)n),
            o_ua = b.take(16 * (size_t)n);
+    const size_t o_wa = warp ? b.take(32 * (size_t)n) : 0, o_ws = warp ? b.take((size_t)n) : 0,
+                 o_wt = warp ? b.take((size_t)n) : 0;
     int rc = c->scratch_a.ensure(b.off);
     if (rc) return rc;
     char* base = (char*)c->scratch_a.ptr;
@@ -385,17 +392,46 @@ int viso_lk_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, i
     a.success = (uint8_t*)(base + o_s);
     a.uv_before = (double*)(base + o_ub);
     a.uv_after = (double*)(base + o_ua);
-    {
+    if (warp) {
+        a.warp_ratio = max_area_ratio;
+        a.warp_A = (double*)(base + o_wa);
+        a.warp_shift = (int8_t*)(base + o_ws);
+        a.warp_status = (uint8_t*)(base + o_wt);
+        TimedRegion t(c->timing, VISO_KERNEL_LKWARP, c->stream);
+        launch_lk_warp(a, c->stream);
+    } else {
         TimedRegion t(c->timing, VISO_KERNEL_LKALIGN, c->stream);
         launch_lk_align(a, c->stream);
     }
     VISO_HIP_CHECK(hipGetLastError());
+    if (warp) {
+        VISO_HIP_CHECK(hipMemcpyAsync(A4, base + o_wa, 32 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        VISO_HIP_CHECK(hipMemcpyAsync(shift, base + o_ws, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        VISO_HIP_CHECK(hipMemcpyAsync(status, base + o_wt, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
     VISO_HIP_CHECK(hipMemcpyAsync(pair_kf, base + o_pk, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(success, base + o_s, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(uv_before, base + o_ub, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(uv_after, base + o_ua, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VISO_OK;
+}
+
+int viso_lk_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                  const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                  const double* points, int32_t n, int32_t* pair_kf, uint8_t* success,
+                  double* uv_before, double* uv_after) {
+    return lk_align_stage(c, kf_pyrs, kf_poses, n_kf, cur_pyr, cur_pose, width, height, points, n, pair_kf, success,
+                          uv_before, uv_after, false, 0.0, nullptr, nullptr, nullptr);
+}
+
+int viso_lk_align_warped(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                         const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                         const double* points, int32_t n, double max_area_ratio, int32_t* pair_kf,
+                         uint8_t* success, double* uv_before, double* uv_after, double* A4, int8_t* shift,
+                         uint8_t* status) {
+    return lk_align_stage(c, kf_pyrs, kf_poses, n_kf, cur_pyr, cur_pose, width, height, points, n, pair_kf, success,
+                          uv_before, uv_after, true, max_area_ratio, A4, shift, status);
 }
 
 }  // extern "C"

@@ -404,6 +404,25 @@ struct viso_ctx {
     bool prefine_on() const { return prefine_interval > 0; }
     int record_obs(int cur);
     int refine_points();
+    // warped LK alignment (viso_set_lk_warp; track.hip lk_warp_kernel): while
+    // on, flush_lk_frames launches the warped kernel over the pending frames
+    // and neither the chunk-resident nor the host grid is used.  warp_buf:
+    // the warp rows, kLkBatch x kMaxMapPoints each: A (4 doubles), shift,
+    // status; allocated while the mode is on.  warp_rows_valid: the last LK
+    // batch was a warped one (its rows belong to lk_last_rows / lk_last_pts)
+    int warp_mode = 0;
+    double warp_ratio = 0.0;
+    int64_t warp_frames = 0;
+    bool warp_rows_valid = false;
+    viso::DevBuf warp_buf;
+    bool warp_on() const { return warp_mode != 0; }
+    double* warp_A() const { return (double*)warp_buf.ptr; }
+    int8_t* warp_shift() const {
+        return (int8_t*)warp_buf.ptr + (size_t)32 * viso::kLkBatch * viso::kMaxMapPoints;
+    }
+    uint8_t* warp_status() const {
+        return (uint8_t*)warp_buf.ptr + (size_t)33 * viso::kLkBatch * viso::kMaxMapPoints;
+    }
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

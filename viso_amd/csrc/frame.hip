@@ -229,7 +229,7 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf, &prefine_buf};
+                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -577,11 +577,22 @@ int viso_ctx::flush_lk_frames(hipStream_t ls, bool keep_last) {
     // frame's ready flag already up (their poses are final), instead of a
     // full-occupancy launch whose workgroups hold the CUs the next frame's
     // direct launches need (VISO_HOST_LK=batch: the latter).
-    const bool grid = side && host_lk_grid();
+    // (the warped alignment, viso_set_lk_warp, runs as its batched launch on
+    // either stream: its template is new work per frame, not the grid's)
+    const bool warp = warp_on();
+    const bool grid = !warp && side && host_lk_grid();
     if (grid) {
         if (int rc = host_grid_args(a, ls)) return rc;
     }
-    {
+    if (warp) {
+        a.warp_ratio = warp_ratio;
+        a.warp_A = warp_A();
+        a.warp_shift = warp_shift();
+        a.warp_status = warp_status();
+        TimedRegion t(timing, VISO_KERNEL_LKWARP, ls);
+        launch_lk_warp(a, ls);
+        warp_frames += a.n_frames;
+    } else {
         TimedRegion t(timing, VISO_KERNEL_LKALIGN, ls);
         if (grid)
             launch_lk_bg(a, n_cu, ls);
@@ -589,6 +600,7 @@ int viso_ctx::flush_lk_frames(hipStream_t ls, bool keep_last) {
             launch_lk_align(a, ls);
     }
     VISO_HIP_CHECK(hipGetLastError());
+    warp_rows_valid = warp;
     if (int rc = count_lk(lk_pending, ls)) return rc;
     lk_last_rows = a.n_frames;
     lk_last_pts = n_map;  // a later keyframe insertion grows n_map, not these rows
@@ -650,8 +662,9 @@ int viso_ctx::finish_host_call() {
     // outside tracking, and with keyframe insertion (its decision reads the
     // frame's nGood at once), pose refinement, point culling or point
     // refinement (every frame is finished inside on_new_frame), as every
-    // other call
-    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || bg_active)
+    // other call; with the warped alignment too (its batched launch, not the
+    // host grid)
+    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || warp_on() || bg_active)
         return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
@@ -684,7 +697,7 @@ bool viso_ctx::host_queue_eligible() {
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
     return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-           bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
+           !warp_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
@@ -806,7 +819,7 @@ int viso_ctx::stage_poses() {
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
                                       lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-                                      !dpend && lk_pending.empty(); }
+                                      !warp_on() && !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1794,6 +1807,90 @@ int viso_get_alignment(viso_ctx* c, int32_t* pair_kf, uint8_t* success, double* 
     }
     VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (n) *n = c->ran_tracking ? (size_t)c->lk_last_pts : 0;
+    return VISO_OK;
+}
+
+// Warped LK alignment (track.hip lk_warp_kernel).  The setter
+// settles pending work first (frames queued with the mode as it was are
+// aligned with it), then allocates or frees the warp rows.
+int viso_set_lk_warp(viso_ctx* c, int32_t mode, double max_area_ratio) {
+    if (!c || (mode != 0 && mode != 1) || (mode == 1 && !(max_area_ratio >= 4.0 && max_area_ratio <= 64.0)))
+        return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    if (mode == 1) {
+        if (!c->warp_on()) {
+            if (int rc = c->warp_buf.ensure((size_t)34 * kLkBatch * kMaxMapPoints)) return rc;
+            c->warp_rows_valid = false;
+            c->warp_frames = 0;
+        }
+        c->warp_ratio = max_area_ratio;
+    } else if (c->warp_on()) {
+        // the last warped batch may still run on the side stream
+        VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+        VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->warp_buf.release();
+        c->warp_rows_valid = false;
+        c->warp_ratio = 0.0;
+    }
+    c->warp_mode = mode;
+    return VISO_OK;
+}
+
+// the last warped row's points, 0 before the first warped batch
+static size_t warp_row_points(const viso_ctx* c) {
+    return (c->warp_on() && c->warp_rows_valid && c->ran_tracking && c->lk_last_rows > 0) ? (size_t)c->lk_last_pts : 0;
+}
+
+int viso_get_lk_warp_rows(viso_ctx* c, double* A4, int8_t* shift, uint8_t* status, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (!c->warp_on()) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+    const size_t pts = warp_row_points(c);
+    const size_t m = std::min(cap, pts);
+    const size_t o = (size_t)std::max(c->lk_last_rows - 1, 0) * kMaxMapPoints;
+    if (m > 0) {
+        if (A4) VISO_HIP_CHECK(hipMemcpyAsync(A4, c->warp_A() + 4 * o, 32 * m, hipMemcpyDeviceToHost, c->stream));
+        if (shift) VISO_HIP_CHECK(hipMemcpyAsync(shift, c->warp_shift() + o, m, hipMemcpyDeviceToHost, c->stream));
+        if (status) VISO_HIP_CHECK(hipMemcpyAsync(status, c->warp_status() + o, m, hipMemcpyDeviceToHost, c->stream));
+    }
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (n) *n = pts;
+    return VISO_OK;
+}
+
+int viso_get_lk_warp(viso_ctx* c, int64_t info[8]) {
+    if (!c || !info) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (!c->warp_on()) return VISO_OK;
+    info[0] = c->warp_mode;
+    info[1] = c->warp_frames;
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+    const size_t m = warp_row_points(c);
+    if (m == 0) return VISO_OK;
+    // the last row's counts, on the host (integer counts of a getter, as
+    // viso_get_frame_stats')
+    const size_t o = (size_t)(c->lk_last_rows - 1) * kMaxMapPoints;
+    std::vector<int32_t> pk(m);
+    std::vector<uint8_t> sc(m), st(m);
+    std::vector<int8_t> sh(m);
+    VISO_HIP_CHECK(hipMemcpyAsync(pk.data(), (int32_t*)c->lk_pair.ptr + o, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(sc.data(), (uint8_t*)c->lk_succ.ptr + o, m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(st.data(), c->warp_status() + o, m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(sh.data(), c->warp_shift() + o, m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < m; ++i) {
+        info[2] += pk[i] >= 0;
+        info[3] += sc[i] != 0;
+        info[4] += (st[i] & 15) == 2;
+        info[5] += sh[i] < 0;
+        info[6] += sh[i] > 0;
+        info[7] += (st[i] >> 4) & 7;
+    }
     return VISO_OK;
 }
 

@@ -127,8 +127,21 @@ struct LkAlignArgs {
     // a resident wave's longest wait for its item's frame before handing the
     // item to the drain (s_memrealtime ticks, 100 MHz)
     unsigned int bg_idle = 30000;
+    // warped alignment (launch_lk_warp; viso_set_lk_warp): the largest area
+    // ratio |det A| (and its inverse) a warp may have, and the per-point warp
+    // rows, laid out as the outputs above (frame f at f * out_stride): A
+    // (4 doubles: A00, A01, A10, A11), the level shift and the status byte
+    double warp_ratio = 0.0;
+    double* warp_A = nullptr;
+    int8_t* warp_shift = nullptr;
+    uint8_t* warp_status = nullptr;
 };
 void launch_lk_align(const LkAlignArgs& a, hipStream_t stream);
+// LK alignment with every keyframe patch warped into the current view by the
+// affine map its point's depth and the two poses imply, and taken from the
+// pyramid level that matches its scale (track.hip lk_warp_kernel; DESIGN.md
+// §17).  The geometry of launch_lk_align; fp64 in both precision modes.
+void launch_lk_warp(const LkAlignArgs& a, hipStream_t stream);
 // LK alignment of an ingest chunk's frames beside its direct-pose chain: grid
 // workgroups (one per CU) resident for the chunk (track.hip lk_item_kernel)
 void launch_lk_bg(const LkAlignArgs& a, int grid, hipStream_t stream);

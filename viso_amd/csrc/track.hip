@@ -809,6 +809,192 @@ __global__ __launch_bounds__(256, FAST ? VISO_LK_MIN_WAVES_FAST : VISO_LK_MIN_WA
     lk_point<FAST>(a, ka, cur, fr.pose, i, (size_t)blockIdx.y * a.out_stride, s_win[wave][0], s_win[wave][1]);
 }
 
+// Warped LK alignment (viso_set_lk_warp): lk_align_kernel's
+// geometry (one wave per (frame, point), lane = patch pixel, blockIdx.y =
+// frame, point groups XCD-stable), with the template of every level sampled
+// per frame from the anchor keyframe through the affine map A (anchor level 0
+// -> current level 0) that the point's depth and the two poses imply, at the
+// reference level r = l + shift that matches its scale.  The iterations are
+// lk_iterate<100, false> on the current level's LDS window, placed as in
+// lk_point.  fp64 in both precision modes.
+constexpr double kWarpH = 4.0;  // the affine map's finite-difference step (anchor pixels)
+
+// a camera point through pose (R row-major + t) and K as project_px does;
+// returns its depth
+__device__ inline double warp_project(const double* pose, const Intrinsics& K, const double* W, double& u,
+                                      double& v) {
+    double c[3];
+    mat3_vec(pose, W, c);
+    c[0] = c[0] + pose[9];
+    c[1] = c[1] + pose[10];
+    c[2] = c[2] + pose[11];
+    const double z = c[2];
+    const double x = c[0] / z, y = c[1] / z;
+    u = x * K.fx + K.cx;
+    v = y * K.fy + K.cy;
+    return z;
+}
+
+__device__ inline bool warp_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+__global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[4][2][kWinW * kWinH];
+    const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (i >= a.n) return;
+    const LkAlignArgs* ka = (const LkAlignArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    const LkFrame& fr = ka->frames[blockIdx.y];
+    const FrameDev cur = fr.cur;
+    const double* cur_pose = fr.pose;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint8_t* my_win0 = s_win[wave][0];
+    uint8_t* my_win1 = s_win[wave][1];
+    const size_t o = (size_t)blockIdx.y * a.out_stride;
+    const int lane = threadIdx.x & 63;
+    const int px = (lane >> 3) - 4, py = (lane & 7) - 4;
+    const double P[3] = {a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]};
+    const Intrinsics K{a.K[0], a.K[1], a.K[2], a.K[3]};
+    const int w0 = a.g.w[0], h0 = a.g.h[0];
+    int32_t kf = -1;
+    uint8_t succ_out = 0, status = 1;
+    int shift = 0;
+    double ub[2] = {0.0, 0.0}, ua[2] = {0.0, 0.0};
+    double A00 = 0.0, A01 = 0.0, A10 = 0.0, A11 = 0.0;
+    double uc, vc;
+    project_px(cur_pose, K, P, 1.0, uc, vc);
+    if (inside_px(uc, vc, w0, h0)) {  // current_frame->IsInside(Pw, 0)
+        double bu, bv;
+        if (a.tmpl_kf) {
+            kf = a.tmpl_kf[i];
+            bu = a.tmpl_uv[2 * i];
+            bv = a.tmpl_uv[2 * i + 1];
+        } else {
+            kf = lk_choose_kf(a, P, bu, bv);
+        }
+        kf = __builtin_amdgcn_readfirstlane(kf);
+        if (kf >= 0) {
+            ub[0] = ua[0] = uc;
+            ub[1] = ua[1] = vc;
+            // the affine map: even lanes carry Qu (bu + h), odd lanes Qv
+            // (bv + h), so the twelve divisions are issued six at a time,
+            // once per wave; the entries are then read from lanes 0 and 1
+            const double* kp = a.kf_poses + 12 * kf;
+            double Pa[3];
+            mat3_vec(kp, P, Pa);
+            const double za = Pa[2] + kp[11];
+            const bool odd = lane & 1;
+            const double qu = odd ? bu : bu + kWarpH, qv = odd ? bv + kWarpH : bv;
+            const double d[3] = {(qu - K.cx) / K.fx * za - kp[9], (qv - K.cy) / K.fy * za - kp[10], za - kp[11]};
+            double Wp[3];
+            for (int j = 0; j < 3; ++j) Wp[j] = (kp[j] * d[0] + kp[3 + j] * d[1]) + kp[6 + j] * d[2];
+            double uq, vq;
+            const double zq = warp_project(cur_pose, K, Wp, uq, vq);
+            const double au = (uq - uc) / kWarpH, av = (vq - vc) / kWarpH;
+            A00 = readlane_f64(au, 0);
+            A10 = readlane_f64(av, 0);
+            A01 = readlane_f64(au, 1);
+            A11 = readlane_f64(av, 1);
+            const double zu = readlane_f64(zq, 0), zv = readlane_f64(zq, 1);
+            const double det = A00 * A11 - A01 * A10;
+            double D = fabs(det);
+            const bool ok = za > 0 && zu > 0 && zv > 0 && warp_finite(A00) && warp_finite(A01) &&
+                            warp_finite(A10) && warp_finite(A11) && 1.0 / a.warp_ratio <= D && D <= a.warp_ratio;
+            status = 2;
+            if (__builtin_amdgcn_readfirstlane(ok ? 1 : 0)) {
+                // the inverse's four divisions on lanes 0..3
+                const int lq = lane & 3;
+                const double num = lq == 0 ? A11 : lq == 1 ? -A01 : lq == 2 ? -A10 : A00;
+                const double q = num / det;
+                const double Ai00 = readlane_f64(q, 0), Ai01 = readlane_f64(q, 1), Ai10 = readlane_f64(q, 2),
+                             Ai11 = readlane_f64(q, 3);
+                if (D > 3.0) {
+                    while (D > 3.0 && shift > -3) {
+                        shift -= 1;
+                        D *= 0.25;
+                    }
+                } else if (D < 1.0 / 3.0) {
+                    while (D < 1.0 / 3.0 && shift < 3) {
+                        shift += 1;
+                        D *= 4.0;
+                    }
+                }
+                shift = __builtin_amdgcn_readfirstlane(shift);
+                const FrameDev& refp = ka->kf[kf];
+                double cu = uc, cv = vc;
+                bool succ = false;
+                int skipped = 0;
+                Window win = load_window(my_win0, level_ptr(cur, kLevels - 1), a.g.w[kLevels - 1],
+                                         a.g.h[kLevels - 1], cu * kScale[kLevels - 1], cv * kScale[kLevels - 1]);
+                for (int level = kLevels - 1; level >= 0; --level) {
+                    const double s = kScale[level];
+                    const int w = a.g.w[level], h = a.g.h[level];
+                    const int r = min(max(level + shift, 0), kLevels - 1);  // wave-uniform
+                    const double sr = r == 0 ? 1.0 : r == 1 ? 0.5 : r == 2 ? 0.25 : 0.125;
+                    const double k = sr / s;  // an exact power of two
+                    const int wr = ka->g.w[r], hr = ka->g.h[r];
+                    const uint8_t* ref = level_ptr(refp, r);
+                    const double x = bu * sr + ((Ai00 * px + Ai01 * py) * k);
+                    const double y = bv * sr + ((Ai10 * px + Ai11 * py) * k);
+                    const double ex0 = Ai00 * k, ex1 = Ai10 * k, ey0 = Ai01 * k, ey1 = Ai11 * k;
+                    const double xs[5] = {x, x + ex0, x - ex0, x + ey0, x - ey0};
+                    const double ys[5] = {y, y + ex1, y - ex1, y + ey1, y - ey1};
+                    bool in = true;
+#pragma unroll
+                    for (int q5 = 0; q5 < 5; ++q5)
+                        in = in && 0 <= xs[q5] && xs[q5] + 1 < wr && 0 <= ys[q5] && ys[q5] + 1 < hr;
+                    if (__builtin_amdgcn_ballot_w64(in) == ~0ull) {
+                        LkTemplate t;
+                        t.I1 = sample_px(ref, wr, hr, xs[0], ys[0]);
+                        t.J0 = -0.5 * (sample_px(ref, wr, hr, xs[1], ys[1]) - sample_px(ref, wr, hr, xs[2], ys[2]));
+                        t.J1 = -0.5 * (sample_px(ref, wr, hr, xs[3], ys[3]) - sample_px(ref, wr, hr, xs[4], ys[4]));
+                        // H and its inverse as lk_prepare forms them
+                        double H00, H01, H11;
+                        wave_tree_sum3(t.J0 * t.J0, t.J0 * t.J1, t.J1 * t.J1, H00, H01, H11);
+                        const double H10 = H01;
+                        const double invdet = 1.0 / (H00 * H11 - H10 * H01);
+                        t.i00 = H11 * invdet;
+                        t.i10 = -H10 * invdet;
+                        t.i01 = -H01 * invdet;
+                        t.i11 = H00 * invdet;
+                        // the bounds test on the current coordinates
+                        const LkResult res = lk_iterate<100, false>(t, w, h, level_ptr(cur, level), w, h, cu * s + px,
+                                                                    cv * s + py, cu * s, cv * s, 0.0, 0.0, a.thresh,
+                                                                    win);
+                        succ = res.succ;
+                        cu = cu + res.dx / s;
+                        cv = cv + res.dy / s;
+                    } else {
+                        succ = false;
+                        skipped += 1;
+                    }
+                    if (level > 0) {
+                        const double s1 = kScale[level - 1];
+                        win = load_window((level & 1) ? my_win0 : my_win1, level_ptr(cur, level - 1),
+                                          a.g.w[level - 1], a.g.h[level - 1], cu * s1, cv * s1);
+                    }
+                }
+                succ_out = succ ? 1 : 0;
+                ua[0] = cu;
+                ua[1] = cv;
+                status = (uint8_t)(skipped << 4);
+            }
+        }
+    }
+    if (lane == 0) {
+        a.pair_kf[o + i] = kf;
+        a.success[o + i] = succ_out;
+        a.uv_before[2 * (o + i)] = ub[0];
+        a.uv_before[2 * (o + i) + 1] = ub[1];
+        a.uv_after[2 * (o + i)] = ua[0];
+        a.uv_after[2 * (o + i) + 1] = ua[1];
+        a.warp_A[4 * (o + i)] = A00;
+        a.warp_A[4 * (o + i) + 1] = A01;
+        a.warp_A[4 * (o + i) + 2] = A10;
+        a.warp_A[4 * (o + i) + 3] = A11;
+        a.warp_shift[o + i] = (int8_t)shift;
+        a.warp_status[o + i] = status;
+    }
+}
+
 // LK alignment in the background of an ingest chunk (viso_ctx::bg_begin;
 // lk_item_kernel):
 // one 256-thread workgroup per CU, resident for the whole chunk beside the
@@ -1158,6 +1344,12 @@ void launch_lk_align(const LkAlignArgs& a, hipStream_t stream) {
         lk_align_kernel<true><<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
     else
         lk_align_kernel<false><<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
+}
+
+void launch_lk_warp(const LkAlignArgs& a, hipStream_t stream) {
+    if (a.n <= 0 || a.n_frames <= 0) return;
+    const int gx = (((a.n + 3) / 4) + 7) / 8 * 8;  // multiple of 8: XCD-stable point groups
+    lk_warp_kernel<<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
 }
 
 // the background kernel's LDS request: static windows + dynamic = 84 KB, so

@@ -231,6 +231,34 @@ class Viso(FrameHandler):
                       ctypes.byref(n))
         return status, steps
 
+    def set_lk_warp(self, mode: int, max_area_ratio: float = 64.0) -> None:
+        """Warped LK alignment (viso_set_lk_warp): every keyframe patch is
+        warped into the current view by the affine map its point's depth and
+        the two poses imply, and taken from the pyramid level that matches
+        its scale; warps whose area ratio is outside [1 / max_area_ratio,
+        max_area_ratio] are rejected.  mode 0 = off."""
+        _lib.call("viso_set_lk_warp", self.ctx.h, int(mode), float(max_area_ratio))
+
+    def lk_warp(self) -> np.ndarray:
+        """viso_get_lk_warp: int64[8] = mode, frames aligned with it, then of
+        the last row: paired, aligned, rejected warps, points with shift < 0,
+        with shift > 0, skipped levels."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_lk_warp", self.ctx.h, info.ctypes.data)
+        return info
+
+    def lk_warp_rows(self):
+        """The last frame's warp rows (viso_get_lk_warp_rows): A (n, 4) =
+        A00, A01, A10, A11; shift (n,) int8; status (n,) uint8."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_lk_warp_rows", self.ctx.h, None, None, None, 0, ctypes.byref(n))
+        A = np.zeros((n.value, 4), np.float64)
+        shift, status = np.zeros(n.value, np.int8), np.zeros(n.value, np.uint8)
+        if n.value:
+            _lib.call("viso_get_lk_warp_rows", self.ctx.h, A.ctypes.data, shift.ctypes.data, status.ctypes.data,
+                      n.value, ctypes.byref(n))
+        return A, shift, status
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
