@@ -436,6 +436,44 @@ public:
         return r;
     }
 
+    // Depth seeds (viso_set_depth_seeds): every corner of a new keyframe that
+    // the map does not cover becomes a seed; every tracking frame searches the
+    // seed's epipolar segment and narrows its inverse depth; every
+    // interval-th frame the converged seeds become map points.  interval 0 =
+    // off.
+    void SetDepthSeeds(int interval, int cell = 16, int max_steps = 32, double depth_min = 2.0,
+                       double depth_max = 60.0, double max_score = 57600.0, double uniqueness = 1.5,
+                       int min_good = 3, double conv_rel = 0.15, int max_bad = 4, int max_lost = 4) {
+        check(viso_set_depth_seeds(ctx_, interval, cell, max_steps, depth_min, depth_max, max_score, uniqueness,
+                                   min_good, conv_rel, max_bad, max_lost),
+              "viso_set_depth_seeds");
+    }
+    // viso_get_depth_seeds' info[8]
+    std::array<int64_t, 8> GetDepthSeeds() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_depth_seeds(ctx_, info.data()), "viso_get_depth_seeds");
+        return info;
+    }
+    // the live seeds' rows: host keyframe, corner (2 per seed), inverse depth,
+    // its variance, counters (4 per seed: good, bad, lost, status)
+    struct DepthSeedRows {
+        std::vector<int32_t> h;
+        std::vector<double> uv, mu, s2;
+        std::vector<int32_t> counters;
+    };
+    DepthSeedRows GetDepthSeedRows() const {
+        size_t n = 0;
+        check(viso_get_depth_seed_rows(ctx_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n),
+              "viso_get_depth_seed_rows");
+        DepthSeedRows r{std::vector<int32_t>(n), std::vector<double>(2 * n), std::vector<double>(n),
+                        std::vector<double>(n), std::vector<int32_t>(4 * n)};
+        if (n)
+            check(viso_get_depth_seed_rows(ctx_, r.h.data(), r.uv.data(), r.mu.data(), r.s2.data(),
+                                           r.counters.data(), n, &n),
+                  "viso_get_depth_seed_rows");
+        return r;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

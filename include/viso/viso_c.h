@@ -188,7 +188,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_CULL 11 /* the record update and cull launches (viso_set_point_cull) */
 #define VISO_KERNEL_POINTS 12 /* the record and refine launches (viso_set_point_refine) */
 #define VISO_KERNEL_LKWARP 13 /* a batched launch of the warped LK alignment (viso_set_lk_warp) */
-#define VISO_KERNEL_COUNT 14
+#define VISO_KERNEL_SEEDS 14 /* the depth seeds' creation, update and promotion launches (viso_depth_seeds_*) */
+#define VISO_KERNEL_COUNT 15
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -578,6 +579,93 @@ int viso_lk_align_warped(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf
                          const double* points, int32_t n_points, double max_area_ratio, int32_t* pair_kf,
                          uint8_t* success, double* uv_before, double* uv_after, double* A4, int8_t* shift,
                          uint8_t* status);
+
+/* Depth seeds (the repo's own spec; no reference counterpart):
+ * the map grows by an epipolar search over the frames after a keyframe.  A
+ * seed is a corner (u, v) of keyframe h (level 0) with an inverse depth mu of
+ * z in h's camera and its variance s2, the counters good, bad and lost and the
+ * status of its last update.  With rho_min = 1 / depth_max and rho_max =
+ * 1 / depth_min a new seed has mu = (rho_min + rho_max) / 2, s2 =
+ * ((rho_max - rho_min) / 4)^2 and counters 0.  The three stages below run on
+ * host data through the launches a frame path uses (VISO_KERNEL_SEEDS); a seed
+ * row travels as h (int32), uv (2 doubles), mu, s2 and counters (4 int32:
+ * good, bad, lost, status).  At most 8192 seeds.  fp64 in both precision
+ * modes.  Every out-of-range or NULL argument returns VISO_ERR_ARG.
+ *
+ * viso_set_depth_seeds switches the mode on in the frame path (interval >= 1;
+ * 0 = off, the default: nothing changes, and the other arguments are not
+ * read).  A seed set is created (see Creation below, with `cell`) whenever a
+ * keyframe is created: at map creation (of the latest keyframe), at a stereo
+ * and at a monocular insertion, behind that step's own points.  Every tracking
+ * frame updates every seed at the frame's final pose (after the pose
+ * refinement, where that is on).  Every interval-th tracking frame, behind
+ * that frame's update and ahead of the cull and the insertion check, the
+ * converged seeds are appended to the map (host = h, a zero track record; the
+ * LK templates are rebuilt when any was appended) and the failed ones are
+ * dropped (see Promotion below).  A retirement (viso_set_map_window) drops the
+ * retired keyframe's seeds and renumbers the others' h.  While on, frames are
+ * finished one by one, as with keyframe insertion.  8 <= cell <= 64, 8 <=
+ * max_steps <= 64, 0 < depth_min < depth_max, max_score > 0, uniqueness >= 1,
+ * 1 <= min_good <= 1000, 0 < conv_rel <= 1, 1 <= max_bad, max_lost <= 1000,
+ * every value finite.  May be called while tracking (pending work is settled
+ * first); switching off frees the seeds. */
+int viso_set_depth_seeds(viso_ctx* ctx, int32_t interval, int32_t cell, int32_t max_steps, double depth_min,
+                         double depth_max, double max_score, double uniqueness, int32_t min_good, double conv_rel,
+                         int32_t max_bad, int32_t max_lost);
+/* info = {interval, live seeds, seeds created in all, promoted in all, dropped
+ * in all (failed or retired with their keyframe), then of the live seeds by
+ * the status of their last update: status 0, status 7-9, status 1-6 (a seed no
+ * update has seen yet is not counted)}.  All 0 while the mode is off. */
+int viso_get_depth_seeds(viso_ctx* ctx, int64_t info[8]);
+/* The live seeds' rows: the first min(cap, n) are written (any output may be
+ * NULL); *n = the live seeds.  VISO_ERR_STATE while the mode is off. */
+int viso_get_depth_seed_rows(viso_ctx* ctx, int32_t* h, double* uv, double* mu, double* s2, int32_t* counters,
+                             size_t cap, size_t* n);
+/*
+ * Creation: the seeds a new keyframe adds.  The map (points, n_points, world)
+ * projected by pose marks the occupancy grid of `cell` (8..64) pixels as a
+ * monocular insertion does; the cell winners of the level-0 image's FAST
+ * corners (the context's fast_thresh and max_features) in the unmarked cells
+ * become seeds of keyframe `host` in corner order, as many as 8192 - n_live.
+ * The first min(cap, appended) rows are written; *n = the seeds appended,
+ * counts = {cell winners, seeds appended}. */
+int viso_depth_seeds_create(viso_ctx* ctx, const uint8_t* image, int32_t width, int32_t height, const double pose[12],
+                            const double* points, int32_t n_points, int32_t cell, int32_t host, double depth_min,
+                            double depth_max, int32_t n_live, int32_t* h, double* uv, double* mu, double* s2,
+                            int32_t* counters, size_t cap, size_t* n, int32_t counts[2]);
+/* Update: one frame (cur_pyr, cur_pose) against n seeds hosted on the n_kf
+ * keyframes (kf_pyrs, kf_poses; every h in [0, n_kf)).  Per seed the segment
+ * mu +- 2 sigma of its epipolar line, clipped to [rho_min, rho_max], is
+ * searched at the finest pyramid level that holds it in max_steps (8..64)
+ * one-pixel steps, for the host patch warped by the affine map of DESIGN.md
+ * §17 (zero-mean sum of squared differences over the 8x8 patch); the best
+ * step, refined by a parabola, gives an inverse depth that is fused into (mu,
+ * s2).  status: 0 fused (good += 1); 1 behind the camera or out of view, 2
+ * warp rejected, 5 template outside the host level, 6 fewer than 3 steps
+ * inside the image (lost += 1 each); 3 segment longer than max_steps at level
+ * 3, 4 shorter than one pixel (nothing changes); 7 best score above max_score,
+ * 8 best score x uniqueness above the best score two or more steps away, 9
+ * depth out of range (bad += 1 each); 0 and 7..9 set lost = 0.  mu, s2 and
+ * counters are updated in place; level_step (may be NULL) receives per seed
+ * the search level and the best step (-1 where not reached).  0 < depth_min <
+ * depth_max, max_score > 0, uniqueness >= 1, all finite. */
+int viso_depth_seeds_update(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                            const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                            int32_t n, int32_t max_steps, double depth_min, double depth_max, double max_score,
+                            double uniqueness, const int32_t* h, const double* uv, double* mu, double* s2,
+                            int32_t* counters, int32_t* level_step);
+/* Promotion.  In seed order: a seed with good >= min_good and s2 <=
+ * (conv_rel mu)^2 has converged; otherwise one with bad >= max_bad or lost >=
+ * max_lost is dropped.  The first `room` converged seeds become the world
+ * points R_h^T (f / mu - t_h) (points, hosts: min(room, n) rows of space);
+ * every seed neither promoted nor dropped survives, and the survivors' rows
+ * are written back compacted in order.  counts = {converged, promoted,
+ * dropped, survivors}.  1 <= min_good, max_bad, max_lost <= 1000, 0 <
+ * conv_rel <= 1, 0 <= room <= 16384. */
+int viso_depth_seeds_promote(viso_ctx* ctx, const double* kf_poses, int32_t n_kf, int32_t n, int32_t min_good,
+                             double conv_rel, int32_t max_bad, int32_t max_lost, int32_t room, int32_t* h, double* uv,
+                             double* mu, double* s2, int32_t* counters, double* points, int32_t* hosts,
+                             int32_t counts[4]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

@@ -19,7 +19,7 @@ ERRORS = {-1: "VISO_ERR_ARG", -2: "VISO_ERR_HIP", -3: "VISO_ERR_CAPACITY",
 STATE_INITIALIZATION, STATE_RUNNING, STATE_FINISHED = 0, 1, 2
 KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "direct": 5,
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
-              "points": 12, "lkwarp": 13}
+              "points": 12, "lkwarp": 13, "seeds": 14}
 
 
 class VisoError(RuntimeError):
@@ -111,6 +111,15 @@ SIGNATURES = {
     "viso_get_lk_warp_rows": [_vp, _vp, _vp, _vp, _sz, _vp],
     "viso_lk_align_warped": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _d, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp],
+    "viso_set_depth_seeds": [_vp, _i32, _i32, _i32, _d, _d, _d, _d, _i32, _d, _i32, _i32],
+    "viso_get_depth_seeds": [_vp, _vp],
+    "viso_get_depth_seed_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "viso_depth_seeds_create": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _d, _d, _i32, _vp, _vp, _vp, _vp,
+                                _vp, _sz, _vp, _vp],
+    "viso_depth_seeds_update": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _d, _d, _d, _d, _vp, _vp, _vp,
+                                _vp, _vp, _vp],
+    "viso_depth_seeds_promote": [_vp, _vp, _i32, _i32, _i32, _d, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp],
     "viso_version": [],
     # north-star stereo VO (include/viso/viso_svo.h)
     "viso_svo_default_params": [_vp, _i32, _i32, _d, _d, _d, _d, _d],

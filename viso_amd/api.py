@@ -155,6 +155,78 @@ class Context:
                   _p(pk), _p(sc), _p(ub), _p(ua), _p(A), _p(sh), _p(st))
         return pk, sc, ub, ua, A, sh, st
 
+    # depth seeds (viso_depth_seeds_*).  Seed rows travel as a
+    # dict: h (n,) int32, uv (n, 2), mu (n,), s2 (n,), cnt (n, 4) int32 =
+    # (good, bad, lost, status).
+    @staticmethod
+    def _seed_rows(rows):
+        r = {"h": np.ascontiguousarray(rows["h"], dtype=np.int32).reshape(-1).copy(),
+             "uv": np.ascontiguousarray(rows["uv"], dtype=np.float64).reshape(-1, 2).copy(),
+             "mu": np.ascontiguousarray(rows["mu"], dtype=np.float64).reshape(-1).copy(),
+             "s2": np.ascontiguousarray(rows["s2"], dtype=np.float64).reshape(-1).copy(),
+             "cnt": np.ascontiguousarray(rows["cnt"], dtype=np.int32).reshape(-1, 4).copy()}
+        n = r["h"].shape[0]
+        if not all(v.shape[0] == n for v in r.values()):
+            raise ValueError("seed rows: one entry per seed in every column")
+        return r, n
+
+    def depth_seeds_create(self, image, pose, points, cell: int = 16, host: int = 0, depth_min: float = 2.0,
+                           depth_max: float = 60.0, n_live: int = 0, cap: int | None = None):
+        """viso_depth_seeds_create: the seeds a new keyframe adds (image its
+        level 0, pose 12 doubles Tcw, points (n, 3) the map).  Returns
+        (rows, counts [cell winners, seeds appended])."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = image.shape
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        pc = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        cells = -(-w // cell) * -(-h // cell) if cell > 0 else 1
+        cap = cells if cap is None else int(cap)
+        m = max(cap, 1)
+        r = {"h": np.zeros(m, np.int32), "uv": np.zeros((m, 2)), "mu": np.zeros(m), "s2": np.zeros(m),
+             "cnt": np.zeros((m, 4), np.int32)}
+        n = ctypes.c_size_t(0)
+        counts = np.zeros(2, np.int32)
+        _lib.call("viso_depth_seeds_create", self.h, _p(image), w, h, _p(pc), _p(pts), pts.shape[0], int(cell),
+                  int(host), float(depth_min), float(depth_max), int(n_live), _p(r["h"]), _p(r["uv"]), _p(r["mu"]),
+                  _p(r["s2"]), _p(r["cnt"]), cap, ctypes.byref(n), _p(counts))
+        k = min(int(n.value), cap)
+        return {key: v[:k].copy() for key, v in r.items()}, [int(c) for c in counts]
+
+    def depth_seeds_update(self, rows, kf_pyrs, kf_poses, cur_pyr, cur_pose, width, height, max_steps: int = 32,
+                           depth_min: float = 2.0, depth_max: float = 60.0, max_score: float = 57600.0,
+                           uniqueness: float = 1.5):
+        """viso_depth_seeds_update: one frame's update of the seed rows.
+        Returns (rows, level_step (n, 2) int32: search level, best step)."""
+        r, n = self._seed_rows(rows)
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple)) else kf_pyrs,
+                                   dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        cp = np.ascontiguousarray(cur_pose, dtype=np.float64).reshape(12)
+        ls = np.full((max(n, 1), 2), -1, np.int32)
+        _lib.call("viso_depth_seeds_update", self.h, _p(kfp), _p(kposes), kposes.shape[0],
+                  _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)), _p(cp), width, height, n, int(max_steps),
+                  float(depth_min), float(depth_max), float(max_score), float(uniqueness), _p(r["h"]), _p(r["uv"]),
+                  _p(r["mu"]), _p(r["s2"]), _p(r["cnt"]), _p(ls))
+        return r, ls[:n]
+
+    def depth_seeds_promote(self, rows, kf_poses, room: int, min_good: int = 3, conv_rel: float = 0.05,
+                            max_bad: int = 4, max_lost: int = 4):
+        """viso_depth_seeds_promote: one promotion.  Returns dict(points
+        (promoted, 3) world, host (promoted,), rows (the survivors), counts
+        [converged, promoted, dropped, survivors])."""
+        r, n = self._seed_rows(rows)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        m = max(min(int(room), n), 1)
+        pts = np.zeros((m, 3), np.float64)
+        hosts = np.zeros(m, np.int32)
+        counts = np.zeros(4, np.int32)
+        _lib.call("viso_depth_seeds_promote", self.h, _p(kposes), kposes.shape[0], n, int(min_good), float(conv_rel),
+                  int(max_bad), int(max_lost), int(room), _p(r["h"]), _p(r["uv"]), _p(r["mu"]), _p(r["s2"]),
+                  _p(r["cnt"]), _p(pts), _p(hosts), _p(counts))
+        np_, ns = int(counts[1]), int(counts[3])
+        return {"points": pts[:np_].copy(), "host": hosts[:np_].copy(),
+                "rows": {key: v[:ns].copy() for key, v in r.items()}, "counts": [int(c) for c in counts]}
+
     def pose_2d2d(self, p1: np.ndarray, p2: np.ndarray, R0=None, T0=None):
         """PoseEstimation2d2d + SelectMotion (src/viso.cpp:178-256, 520-638) on
         normalised (n,3) points.  Returns dict(R, T, inliers, points3d,

@@ -423,6 +423,31 @@ struct viso_ctx {
     uint8_t* warp_status() const {
         return (uint8_t*)warp_buf.ptr + (size_t)33 * viso::kLkBatch * viso::kMaxMapPoints;
     }
+    // depth seeds (viso_set_depth_seeds; depthseed.hip): every keyframe
+    // creation adds a seed set (the cell winners of its corners in the cells
+    // the map leaves unmarked), every tracking frame updates every seed at its
+    // final pose (the frame is finished inside on_new_frame, as for the pose
+    // refinement), every seed_interval-th tracking frame converged seeds
+    // become map points and failed ones are dropped.  0 = off (seed_buf
+    // null).  seed_last: {frames at the last promotion (-1: none), the points
+    // it appended, the seeds it dropped}
+    int seed_interval = 0, seed_cell = 16, seed_max_steps = 0, seed_min_good = 0, seed_max_bad = 0, seed_max_lost = 0;
+    double seed_dmin = 0.0, seed_dmax = 0.0, seed_max_score = 0.0, seed_uniqueness = 0.0, seed_conv_rel = 0.0;
+    int n_seeds = 0;
+    int64_t seeds_created = 0, seeds_promoted = 0, seeds_dropped = 0, seeds_retired = 0, seed_updates = 0;
+    int64_t seed_last[3] = {-1, 0, 0};
+    viso::DevBuf seed_buf;
+    bool seeds_on() const { return seed_interval > 0; }
+    viso::SeedRows seed_rows() const;
+    int* seed_counts() const;
+    int create_seeds(int cur, bool fresh);
+    int update_seeds(int cur);
+    int promote_seeds();
+    int retire_seeds();
+    // the candidate launches of one seed set (FAST on level0, the map's
+    // occupancy, the cell winners in corner order: a.win_xy, a.counts[1])
+    int seed_candidates(viso::MonoKfArgs& a, const uint8_t* level0, const viso::PyrGeom& g, viso::FastScratch& fs,
+                        const double* pose_c, const double* points, int n_points);
 
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;

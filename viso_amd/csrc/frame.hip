@@ -229,7 +229,7 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf};
+                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -664,7 +664,8 @@ int viso_ctx::finish_host_call() {
     // refinement (every frame is finished inside on_new_frame), as every
     // other call; with the warped alignment too (its batched launch, not the
     // host grid)
-    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || warp_on() || bg_active)
+    if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || warp_on() || seeds_on() ||
+        bg_active)
         return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
@@ -697,7 +698,7 @@ bool viso_ctx::host_queue_eligible() {
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
     return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-           !warp_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
+           !warp_on() && !seeds_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
@@ -819,7 +820,7 @@ int viso_ctx::stage_poses() {
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
                                       lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-                                      !warp_on() && !dpend && lk_pending.empty(); }
+                                      !warp_on() && !seeds_on() && !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1146,7 +1147,7 @@ int viso_ctx::append_keyframe(int cur, int m) {
     rc = build_lk_templates();
     if (rc) return rc;
     stats[14] = m;
-    return VISO_OK;
+    return create_seeds(cur, false);  // (viso_set_depth_seeds: the new keyframe's seed set)
 }
 
 // Stereo initialisation (the repo's own spec, oracle/oracle_stereo.cpp
@@ -1176,7 +1177,7 @@ int viso_ctx::stereo_init(int cur, bool* made) {
     stats[3] = -2;  // stereo initialisation
     stats[12] = 1;
     *made = true;
-    return VISO_OK;
+    return create_seeds(cur, true);  // (viso_set_depth_seeds: the first keyframe's seed set)
 }
 
 // ------------------------------------------------------------------ OnNewFrame
@@ -1351,6 +1352,8 @@ int viso_ctx::on_new_frame(int cur) {
                     state = p.enable_tracking ? VISO_STATE_RUNNING : VISO_STATE_FINISHED;
                     stats[12] = 1;
                     counted = false;  // `break` skips ++frame_cnt (src/viso.cpp:98)
+                    // (viso_set_depth_seeds: the seed set of the latest keyframe, cur)
+                    if (const int rc = create_seeds(cur, true)) return rc;
                 }
             } else {
                 // re-detect (src/viso.cpp:100-108)
@@ -1442,7 +1445,7 @@ int viso_ctx::on_new_frame(int cur) {
             // pose refinement (viso_set_pose_refine, refine.hip): this frame's
             // final solve and its LK alignment now, then the refine launch on
             // that LK row; everything below and the next frame see its pose
-            if ((refine_on() || cull_on() || prefine_on()) && n_map > 0) {
+            if ((refine_on() || cull_on() || prefine_on() || seeds_on()) && n_map > 0) {
                 int rc = finish_call(stream);
                 if (!rc && refine_on()) rc = refine_frame(cur);
                 // map point culling (viso_set_point_cull, pointcull.hip):
@@ -1452,6 +1455,9 @@ int viso_ctx::on_new_frame(int cur) {
                 // point refinement (viso_set_point_refine, pointrefine.hip):
                 // the frame's final pose and LK row into the observation ring
                 if (!rc && prefine_on()) rc = record_obs(cur);
+                // depth seeds (viso_set_depth_seeds, depthseed.hip): every
+                // seed's epipolar search in this frame at its final pose
+                if (!rc && seeds_on()) rc = update_seeds(cur);
                 if (rc) return rc;
             }
             // keyframe insertion (stereo: oracle_viso.cpp; monocular:
@@ -1463,6 +1469,13 @@ int viso_ctx::on_new_frame(int cur) {
             // cull and the insertion check (no host sync)
             if (prefine_on() && n_map > 0 && track_cnt % prefine_interval == 0) {
                 const int rc = refine_points();
+                if (rc) return rc;
+            }
+            // every seed_interval-th tracking frame the converged seeds become
+            // map points and the failed ones leave, behind this frame's update
+            // and ahead of the cull and the insertion check (one host sync)
+            if (seeds_on() && n_map > 0 && track_cnt % seed_interval == 0) {
+                const int rc = promote_seeds();
                 if (rc) return rc;
             }
             // every cull_interval-th tracking frame the points that kept

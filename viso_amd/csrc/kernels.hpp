@@ -217,6 +217,65 @@ void launch_mono_candidates(const MonoKfArgs& a, hipStream_t stream);
 // of the accepted points into out; counts[2..3]
 void launch_mono_triangulate(const MonoKfArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- depth seeds
+// viso_set_depth_seeds (depthseed.hip): everything in device
+// memory.  A seed row: host keyframe h, corner uv (host level 0), inverse
+// depth mu and its variance s2, cnt = {good, bad, lost, last status}.
+constexpr int kMaxSeeds = 8192;
+constexpr double kSeedAreaRatio = 64.0;  // a seed's warp is rejected outside 1/64 <= |det A| <= 64
+struct SeedRows {
+    int32_t* h;
+    double* uv;  // 2 per seed
+    double* mu;
+    double* s2;
+    int4* cnt;
+};
+// rows of n seeds carved from seed_rows_bytes(n) bytes
+size_t seed_rows_bytes(int n);
+size_t seed_rows_at(SeedRows& r, void* base, int n);
+struct SeedUpdateArgs {
+    FrameDev kf[kMaxKeyframes];
+    const double* kf_poses;  // n_kf x 12 (device)
+    int n_kf;
+    FrameDev cur;
+    const double* cur_pose;  // 12
+    struct {
+        int w[4], h[4];
+    } g;
+    double K[4];
+    struct {
+        int max_steps;
+        double rho_min, rho_max, max_score, uniqueness;
+    } p;
+    SeedRows rows;  // updated in place
+    int n;
+    int2* diag;  // per seed {search level, best step} (-1: not reached), or null
+};
+// one frame's update: one wave per seed
+void launch_seed_update(const SeedUpdateArgs& a, hipStream_t stream);
+struct SeedPromoteArgs {
+    SeedRows rows;  // survivors compacted in place, in order
+    int n;
+    const double* kf_poses;
+    double K[4];
+    int min_good, max_bad, max_lost;
+    double conv_rel;
+    int room;          // points that fit
+    double* out_pts;   // room x 3 (world), in seed order
+    int32_t* out_host;
+    int* counts;       // {converged, promoted, dropped, survivors}
+};
+void launch_seed_promote(const SeedPromoteArgs& a, hipStream_t stream);
+// keyframe 0 retired: its seeds leave, the others' h moves down; counts[0] = survivors
+void launch_seed_retire(const SeedRows& rows, int n, int* counts, hipStream_t stream);
+bool seed_params_ok(int max_steps, double depth_min, double depth_max, double max_score, double uniqueness);
+bool seed_promote_params_ok(int min_good, double conv_rel, int max_bad, int max_lost);
+// behind launch_mono_candidates: the winners (m.win_xy, m.counts[1]) become
+// fresh rows from row dst on, at most kMaxSeeds - n_live of them; counts =
+// {winners, seeds appended} (device)
+void launch_seed_rows(const SeedRows& rows, const MonoKfArgs& m, int n_live, int dst, int host, double depth_min,
+                      double depth_max, int* counts, hipStream_t stream);
+
 // ---------------------------------------------------------------- sliding-window map
 // One retirement of viso_set_map_window (mapwin.hip): keyframe 0 leaves, the
 // check frame is c.  Poses, points and hosts in device memory; the scratch

@@ -266,7 +266,7 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     win_last[2] = h_int[11];
     win_last[3] = kept;
     *retired = true;
-    return VISO_OK;
+    return retire_seeds();  // (viso_set_depth_seeds: the retired keyframe's seeds go with it)
 }
 
 extern "C" {

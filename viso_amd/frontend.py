@@ -231,6 +231,40 @@ class Viso(FrameHandler):
                       ctypes.byref(n))
         return status, steps
 
+    def set_depth_seeds(self, interval: int, cell: int = 16, max_steps: int = 32, depth_min: float = 2.0,
+                        depth_max: float = 60.0, max_score: float = 57600.0, uniqueness: float = 1.5,
+                        min_good: int = 3, conv_rel: float = 0.15, max_bad: int = 4, max_lost: int = 4) -> None:
+        """Depth seeds (viso_set_depth_seeds): every corner of a new keyframe
+        that the map does not cover becomes a seed with the inverse depth range
+        [1 / depth_max, 1 / depth_min]; every tracking frame searches each
+        seed's epipolar segment (at most max_steps one-pixel steps) and narrows
+        the range; every `interval`-th tracking frame the converged seeds
+        become map points and the failed ones are dropped.  0 = off."""
+        _lib.call("viso_set_depth_seeds", self.ctx.h, int(interval), int(cell), int(max_steps), float(depth_min),
+                  float(depth_max), float(max_score), float(uniqueness), int(min_good), float(conv_rel), int(max_bad),
+                  int(max_lost))
+
+    def depth_seeds(self) -> np.ndarray:
+        """viso_get_depth_seeds: int64[8] = interval, live seeds, created,
+        promoted and dropped in all, then of the live seeds by their last
+        update: status 0, status 7-9, status 1-6."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_depth_seeds", self.ctx.h, info.ctypes.data)
+        return info
+
+    def depth_seed_rows(self) -> dict:
+        """The live seeds' rows (viso_get_depth_seed_rows): h (n,) int32, uv
+        (n, 2), mu (n,), s2 (n,), cnt (n, 4) int32 = good, bad, lost, status."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_depth_seed_rows", self.ctx.h, None, None, None, None, None, 0, ctypes.byref(n))
+        m = max(int(n.value), 1)
+        r = {"h": np.zeros(m, np.int32), "uv": np.zeros((m, 2)), "mu": np.zeros(m), "s2": np.zeros(m),
+             "cnt": np.zeros((m, 4), np.int32)}
+        if n.value:
+            _lib.call("viso_get_depth_seed_rows", self.ctx.h, r["h"].ctypes.data, r["uv"].ctypes.data,
+                      r["mu"].ctypes.data, r["s2"].ctypes.data, r["cnt"].ctypes.data, n.value, ctypes.byref(n))
+        return {k: v[:n.value] for k, v in r.items()}
+
     def set_lk_warp(self, mode: int, max_area_ratio: float = 64.0) -> None:
         """Warped LK alignment (viso_set_lk_warp): every keyframe patch is
         warped into the current view by the affine map its point's depth and
