@@ -43,7 +43,7 @@ def main():
     lib.viso_debug_probe_ring.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_int]
     cap = 4096
-    log = np.zeros((cap, 16), np.uint64)
+    log = np.zeros((cap, 24), np.uint64)
     exits = np.zeros(cap, np.uint64)
     nl = ctypes.c_int(0)
 
@@ -109,6 +109,15 @@ def main():
     for k, name in enumerate(names, start=1):
         if name == "-":
             continue
+        row = []
+        for m in kinds:
+            sel = m & (log[:, k] > 0)
+            row.append(f"{(log[sel, k] - entry[sel]).mean() * us:7.2f}" if sel.any() else "      -")
+        print(f"  {name:52s}" + "  ".join(row))
+    # the prologue's split (wave 0 of block 0 unless said)
+    for k, name in [(16, "past the first LDS barrier"), (17, "partial loads returned (w0)"),
+                    (18, "wave tree stored (w0)"), (19, "arrival count at 5"),
+                    (20, "wave 5 past its state load")]:
         row = []
         for m in kinds:
             sel = m & (log[:, k] > 0)

@@ -47,7 +47,7 @@ def main():
     lib.viso_debug_probe_ring.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_int]
     rcap = 4096
-    rlog = np.zeros((rcap, 16), np.uint64)
+    rlog = np.zeros((rcap, 24), np.uint64)  # direct.hip kPSt stamps per launch
     rexit = np.zeros(rcap, np.uint64)
     nl = ctypes.c_int(0)
 

@@ -38,7 +38,7 @@ def main():
     lib.viso_debug_probe_ring.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_int]
     cap = 4096
-    log = np.zeros((cap, 16), np.uint64)
+    log = np.zeros((cap, 24), np.uint64)  # direct.hip kPSt stamps per launch
     exits = np.zeros(cap, np.uint64)
     nl = ctypes.c_int(0)
     assert lib.viso_debug_probe_ring(log.ctypes.data, exits.ctypes.data, cap, ctypes.byref(nl), 1) == 0

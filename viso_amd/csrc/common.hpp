@@ -281,6 +281,50 @@ __device__ inline double swizzle_xor16_f64(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// The same tree over 64 leaves whose first level (leaf 2 p + leaf 2 p + 1) is
+// already formed: lane p < 32 holds in a[k] the pair p's sum of value k, lane
+// 32 + p its sum of value 14 + k (what the first level below keeps in lanes
+// 2 p and 2 p + 1).  The remaining levels pair p with p ^ 1, ^ 2, ^ 4, ^ 8,
+// ^ 16 -- leaves ^ 2 .. ^ 32, the ascending-xor order -- and every partial sum
+// is the one reduce_scatter_28 forms.  On return lane l (and l ^ 16) holds
+// value index 14*b5 + 7*b0 + 4*b1 + 2*b2 + b3 when 4*b1 + 2*b2 + b3 < 7.
+__device__ inline double reduce_scatter_28_paired(const double* a, int* value_index) {
+    const int lane = threadIdx.x & 63;
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8, b5 = lane & 32;
+    double c[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const double send = dsel(b0, a[k], a[7 + k]);
+        const double keep = dsel(b0, a[7 + k], a[k]);
+        c[k] = keep + dpp_f64<0xB1>(send);
+    }
+    double d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double hi = k < 3 ? c[4 + k] : 0.0;
+        const double send = dsel(b1, c[k], hi);
+        const double keep = dsel(b1, hi, c[k]);
+        d[k] = keep + dpp_f64<0x4E>(send);
+    }
+    double e[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double send = dsel(b2, d[k], d[2 + k]);
+        const double keep = dsel(b2, d[2 + k], d[k]);
+        const double recv = dsel(b2, dpp_f64<0x114>(send), dpp_f64<0x104>(send));  // row_shr:4 / row_shl:4
+        e[k] = keep + recv;
+    }
+    const double send = dsel(b3, e[0], e[1]);
+    const double keep = dsel(b3, e[1], e[0]);
+    double f = keep + dpp_f64<0x128>(send);  // row_ror:8 = the xor-8 partner
+    double ra, rb;
+    permlane16_swap_f64(f, f, ra, rb);  // xor 16: row pairs (0,1), (2,3)
+    f = ra + rb;
+    const int local = (b1 ? 4 : 0) + (b2 ? 2 : 0) + (b3 ? 1 : 0);
+    *value_index = local >= 7 ? -1 : (b5 ? 14 : 0) + (b0 ? 7 : 0) + local;
+    return f;
+}
+
 __device__ inline double reduce_scatter_28(const double* v, int* value_index) {
     const int lane = threadIdx.x & 63;
     const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8, b4 = lane & 16;

@@ -55,10 +55,15 @@
 // reduced, 2 the solver starts (S combined), 3 LU, 4 inverse, 5 update,
 // 6 SE3 exp, 7 solve finished, 8 after B2, 9 the last prefetch wave of block
 // 0 done (LDS max), 10 block 0's tiles evaluated, 11 block 0 exit; 15 meta =
-// (level + 1) | merged << 8 | n_tiles << 16.
+// (level + 1) | merged << 8 | n_tiles << 16.  The prologue's split (wave 0
+// unless said): 16 past the first LDS barrier, 17 its partial loads returned
+// (behind an s_waitcnt vmcnt(0) of the probe build; reduce_scatter_28 waits
+// there anyway), 18 its wave tree stored, 19 the arrival count seen at 5,
+// 20 wave 5 (the first prefetch wave with no partials to load) past its
+// state load.
 #ifdef VISO_PROBE
 constexpr int kPRing = 4096;
-constexpr int kPSt = 16;
+constexpr int kPSt = 24;
 __device__ unsigned long long g_plog[kPRing][kPSt];
 __device__ unsigned long long g_pexit[kPRing];
 // per-block entry / exit stamps of the last kPRingB launches
@@ -1281,6 +1286,34 @@ __device__ inline void load_partials(const double* __restrict__ part, const int*
     }
 }
 
+// The same with the canonical tree's first level (tile 2 p + tile 2 p + 1)
+// taken in the load: the two tiles of one sum are neighbours in the k-major
+// layout, so one 16-byte load brings both addends.  Lane p < 32 of wave w
+// takes the pair p of the wave's 64 tiles for sums 0..13, lane 32 + p the
+// same pair for sums 14..27: fourteen loads per lane instead of 28, each one
+// two contiguous 512-byte runs, and the level's selects and DPP moves go
+// (a + b == b + a bit for bit; a tile beyond n_tiles is the +0.0 it was).
+// a[14] feeds reduce_scatter_28_paired; gg stays tile t's count.
+__device__ inline void load_partials_paired(const double* __restrict__ part, const int* __restrict__ good,
+                                            int n_tiles, double* a, int& gg) {
+    const int t = threadIdx.x;
+    const int t0 = (t & ~63) + 2 * (t & 31);
+    if (t0 < n_tiles) {
+        const bool has1 = t0 + 1 < n_tiles;
+        const double2* __restrict__ p2 =
+            reinterpret_cast<const double2*>(part + ((t & 32) ? (size_t)(kSums / 2) * kMaxTiles : 0) + t0);
+#pragma unroll
+        for (int k = 0; k < kSums / 2; ++k) {
+            const double2 x = p2[(size_t)k * (kMaxTiles / 2)];
+            a[k] = x.x + (has1 ? x.y : 0.0);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kSums / 2; ++k) a[k] = 0.0;
+    }
+    gg = t < n_tiles ? good[t] : 0;
+}
+
 // Canonical tree over <= 256 tiles (thread t holds tile t) -> L.S, L.ngood.
 __device__ inline void reduce_partials(const double* v, int gg, SolveLds& L) {
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -1443,9 +1476,9 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
     // while the workgroup's waves arrive at the first barrier: the partials
     // of level sl (waves 0-3) and the T21 that level was evaluated at (thread
     // 256; every prefetch wave for its prediction)
-    double v[kSums];
+    double v[kSums / 2];  // the tree's first level is taken in the load
     int gg = 0;
-    if (((pre_hdr >> 16) & 1) && t < 256) load_partials(pre_part, pre_good, pre_hdr & 0xffff, v, gg);
+    if (((pre_hdr >> 16) & 1) && t < 256) load_partials_paired(pre_part, pre_good, pre_hdr & 0xffff, v, gg);
     const bool pf_wave = !solve || (wave & 3) != 0;
     double st[7];
     if (t == 256 || (solve && tiles && pf_wave)) {
@@ -1472,6 +1505,7 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
     }
     if (SP && t >= kThreads - kSpPoints) s_sp.ready[kThreads - 1 - t] = 0;
     lds_barrier();  // the LDS words above; the global loads stay in flight
+    if (wave == 0) PST(16);
 
     if (t == 256) {
         for (int k = 0; k < 7; ++k) {
@@ -1485,12 +1519,17 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         atomicAdd(&s_arrive, 1);
     }
     if (solve && t < 256) {
+#ifdef VISO_PROBE
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (wave == 0) PST(17);
+#endif
         int idx;
-        const double f = reduce_scatter_28(v, &idx);
-        if (lane < 32 && idx >= 0) L.red[wave][idx] = f;
+        const double f = reduce_scatter_28_paired(v, &idx);
+        if (!(lane & 16) && idx >= 0) L.red[wave][idx] = f;
         const int g = wave_sum_int(gg);
         if (lane == 0) L.g[wave] = g;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (wave == 0) PST(18);
         if (lane == 0) atomicAdd(&s_arrive, 1);
     }
     if (wave == 0) PST(1);
@@ -1507,6 +1546,12 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         if (!solve) {
             for (int k = 0; k < 12; ++k) pred[k] = a.pose_seed[k];
         } else {
+#ifdef VISO_PROBE
+            if (wave == 5) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                PST(20);
+            }
+#endif
             state_to_pose(st, pred);  // loaded above
         }
         const int first = solve ? wave - (wave >> 2) - 1 : wave;
@@ -1525,6 +1570,7 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         __builtin_amdgcn_s_setprio(3);
         while (__hip_atomic_load(&s_arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 5)
             __builtin_amdgcn_s_sleep(1);
+        PST(19);
         // canonical tree, last level: (w0 + w1) + (w2 + w3)
         if (lane < kSums) L.S[lane] = (L.red[0][lane] + L.red[1][lane]) + (L.red[2][lane] + L.red[3][lane]);
         if (lane == 0) L.ngood = (L.g[0] + L.g[1]) + (L.g[2] + L.g[3]);
@@ -2322,7 +2368,7 @@ void launch_direct_pose(const FrameDev& last_pyr, const FrameDev& cur_pyr, const
 
 #ifdef VISO_PROBE
 // The direct-pose probe ring: *n_launches = launches since the last reset;
-// log (cap x 16 stamps) and exits (cap) in launch order for the last
+// log (cap x 24 stamps) and exits (cap) in launch order for the last
 // min(cap, n, 4096) launches.
 extern "C" int viso_debug_probe_ring(unsigned long long* log, unsigned long long* exits, int cap, int* n_launches,
                                      int reset) {

@@ -144,6 +144,7 @@ __device__ __attribute__((always_inline)) inline void solve_after_lu(SolveLds& L
 // L.state and the loop decision L.cont (src/viso.cpp:731-753), with the LU
 // replicated in every lane's registers (the
 // product's solve: solve_wave0 below).
+template <bool QL = false>
 __device__ __attribute__((always_inline)) inline void solve_wave0_rep(SolveLds& L, int iter, double* stats,
                                    unsigned long long* stamps = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -198,8 +199,21 @@ __device__ __attribute__((always_inline)) inline void solve_wave0_rep(SolveLds& 
                 }
             }
             const double piv = A[7 * k];
+            if (QL && k < 4) {
+                // the step's 5 - k quotients by one division sequence: lane
+                // j takes A[k + 1 + j][k] as its dividend, and the quotients
+                // come back into every lane's copy by readlane (each lane
+                // performs the IEEE division the loop below performs)
+                double num = A[6 * (k + 1) + k];
 #pragma unroll
-            for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / piv;
+                for (int i = k + 2; i < 6; ++i) num = (lane == i - k - 1) ? A[6 * i + k] : num;
+                const double q = num / piv;
+#pragma unroll
+                for (int i = k + 1; i < 6; ++i) A[6 * i + k] = readlane_f64(q, i - k - 1);
+            } else {
+#pragma unroll
+                for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / piv;
+            }
         }
 #pragma unroll
         for (int i = k + 1; i < 6; ++i)
@@ -340,12 +354,19 @@ __device__ __attribute__((always_inline)) inline void solve_wave0_lane(SolveLds&
 }
 
 
+// The product's faithful solve: the replicated LU with the quotients of LU
+// steps 0-3 on lanes (QL; -DVISO_SOLVE_QL=0 builds the plain form for an
+// A/B).  The result bits are solve_wave0_rep<false>'s
+// (tools/ubench/solve_bench.hip compares the hashes).
+#ifndef VISO_SOLVE_QL
+#define VISO_SOLVE_QL 1
+#endif
 __device__ __attribute__((always_inline)) inline void solve_wave0(SolveLds& L, int iter, double* stats,
                                                                    unsigned long long* stamps = nullptr) {
 #ifdef VISO_SOLVE_LANE
     solve_wave0_lane(L, iter, stats, stamps);
 #else
-    solve_wave0_rep(L, iter, stats, stamps);
+    solve_wave0_rep<VISO_SOLVE_QL>(L, iter, stats, stamps);
 #endif
 }
 
