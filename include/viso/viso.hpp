@@ -315,6 +315,17 @@ public:
         return s;
     }
 
+    // viso_direct_solve: the faithful solve of one direct-pose level on given
+    // sums (28), nGood and T21 (7) -> {stats[50], the new T21}
+    std::pair<std::array<double, 50>, std::array<double, 7>> DirectSolve(const std::array<double, 28>& sums,
+                                                                         int n_good,
+                                                                         const std::array<double, 7>& state) const {
+        std::pair<std::array<double, 50>, std::array<double, 7>> out{};
+        check(viso_direct_solve(ctx_, sums.data(), n_good, state.data(), out.first.data(), out.second.data()),
+              "viso_direct_solve");
+        return out;
+    }
+
     // Map growth for the monocular path (viso_set_mono_keyframes: the
     // triangulation Viso::Reconstruct, src/viso.cpp:434-501, sketches), and
     // the photometric BA after each insertion (viso_set_bundle_adjust).

@@ -229,6 +229,16 @@ int viso_direct_pose(viso_ctx* ctx, const uint8_t* last_pyr, const uint8_t* cur_
                      int32_t width, int32_t height, const double* points, int32_t n_points,
                      const double pose_last[12], double pose_io[12]);
 
+/* The serial Gauss-Newton step of one direct-pose level
+ * (DirectPoseEstimationSingleLayer, src/viso.cpp:731-753, first iteration) on
+ * given sums, by the faithful solve of the level kernels: sums[28] = the 21
+ * upper-triangle entries of H (row-major), b (6), the cost sum; n_good;
+ * state[7] = T21 as quaternion (x, y, z, w) and translation.  stats[50] =
+ * {nGood, cost / nGood, H (36), b (6), update (6)}; state_out[7] = the new
+ * T21 (the given one when the update is NaN). */
+int viso_direct_solve(viso_ctx* ctx, const double sums[28], int32_t n_good, const double state[7],
+                      double stats[50], double state_out[7]);
+
 /* LKAlignment (src/viso.cpp:768-843) against n_kf keyframes. */
 int viso_lk_align(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
                   const uint8_t* cur_pyr, const double cur_pose[12], int32_t width,

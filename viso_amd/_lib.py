@@ -76,6 +76,7 @@ SIGNATURES = {
     "viso_fast": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp],
     "viso_klt": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32],
     "viso_direct_pose": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],
+    "viso_direct_solve": [_vp, _vp, _i32, _vp, _vp, _vp],
     "viso_lk_align": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
                       _vp],
     "viso_pose_2d2d": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -114,6 +114,17 @@ class Context:
                   _p(pl), _p(pio))
         return pio
 
+    def direct_solve(self, sums, n_good, state):
+        """viso_direct_solve: the faithful Gauss-Newton solve of one level
+        (first iteration) on 28 sums, nGood and T21 (7).  Returns (stats (50,)
+        = [nGood, cost, H (36), b (6), update (6)], state_out (7,))."""
+        s = np.ascontiguousarray(sums, dtype=np.float64).reshape(28)
+        st = np.ascontiguousarray(state, dtype=np.float64).reshape(7)
+        stats = np.zeros(50, np.float64)
+        out = np.zeros(7, np.float64)
+        _lib.call("viso_direct_solve", self.h, _p(s), int(n_good), _p(st), _p(stats), _p(out))
+        return stats, out
+
     def lk_align(self, kf_pyrs, kf_poses, cur_pyr, cur_pose, width, height, points):
         """LKAlignment (src/viso.cpp:768-843): dense per-map-point outputs
         (pair_kf, success, uv_before (n,2), uv_after (n,2))."""

@@ -336,6 +336,27 @@ int viso_direct_pose(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_py
     return VISO_OK;
 }
 
+int viso_direct_solve(viso_ctx* c, const double sums[28], int32_t n_good, const double state[7],
+                      double stats[50], double state_out[7]) {
+    if (!c || !sums || !state || !stats || !state_out) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    Bump b;
+    size_t o_s = b.take(28 * 8), o_st = b.take(7 * 8), o_out = b.take(50 * 8), o_so = b.take(7 * 8);
+    int rc = c->scratch_a.ensure(b.off);
+    if (rc) return rc;
+    char* base = (char*)c->scratch_a.ptr;
+    VISO_HIP_CHECK(hipMemcpyAsync(base + o_s, sums, 28 * 8, hipMemcpyHostToDevice, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(base + o_st, state, 7 * 8, hipMemcpyHostToDevice, c->stream));
+    launch_direct_solve((const double*)(base + o_s), n_good, (const double*)(base + o_st), (double*)(base + o_out),
+                        (double*)(base + o_so), c->stream);
+    VISO_HIP_CHECK(hipGetLastError());
+    VISO_HIP_CHECK(hipMemcpyAsync(stats, base + o_out, 50 * 8, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(state_out, base + o_so, 7 * 8, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VISO_OK;
+}
+
 // viso_lk_align (warp == false) and viso_lk_align_warped: the same staging,
 // the batched kernel or the warped one
 static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,

@@ -1144,7 +1144,18 @@ __device__ inline void scalar_pass(const DirectArgs& a, int lv, const double* cu
 // keeps the block-barrier form.
 constexpr unsigned kSrcHere = 0xffffffffu;  // direct_tile_pf: factored_sources() computed there
 
-template <bool FAST, bool LV16 = false, int W = kWaves>
+// Where sum k of tile b lies in a level's partials.  k-major ([28][256]: the
+// continuation's and the rig's scratch, read by load_partials and the rig's
+// reader), or PAIRED ([14][4 waves][2][64]: sum k + 14 h of tile 64 w + j at
+// [k][w][h][j], the level scratch load_partials_paired reads).
+template <bool PAIRED>
+__device__ inline size_t partial_index(int k, int b) {
+    if (!PAIRED) return (size_t)k * kMaxTiles + b;
+    const int h = k >= kSums / 2 ? 1 : 0;
+    return (size_t)((((k - h * (kSums / 2)) * 4 + (b >> 6)) * 2 + h) * 64 + (b & 63));
+}
+
+template <bool FAST, bool LV16 = false, int W = kWaves, bool PAIRED = false>
 __device__ void direct_tile_pf(const DirectArgs& a, const LevelPair& fp, int lv, const double* cur_pose, int b,
                                const PfLds& pf, bool merged, double* part, int* good, double* s_pts,
                                int* s_good, int* s_cnt = nullptr, double* s_qt = nullptr,
@@ -1239,7 +1250,7 @@ __device__ void direct_tile_pf(const DirectArgs& a, const LevelPair& fp, int lv,
                 for (int j = 0; j < 16; j += 2 * st) v[j] = v[j] + v[j + st];
             double r = v[0] + 0.0;  // lanes 16..31 (+0)
             r = r + 0.0;            // the other half wave (+0)
-            part[(size_t)lane * kMaxTiles + b] = r;  // k-major: [28][256]
+            part[partial_index<PAIRED>(lane, b)] = r;
         }
         if (lane == 0) good[b] = __hip_atomic_load(s_good, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef VISO_PROBE
@@ -1252,7 +1263,7 @@ __device__ void direct_tile_pf(const DirectArgs& a, const LevelPair& fp, int lv,
     for (int k = wave; k < kSums; k += W) {
         const double v = lane < T ? s_pts[lane * kSums + k] : 0.0;
         const double r = wave_tree_sum_dpp(v);
-        if (lane == 0) part[(size_t)k * kMaxTiles + b] = r;  // k-major: [28][256]
+        if (lane == 0) part[partial_index<PAIRED>(k, b)] = r;
     }
     if (threadIdx.x == 0) good[b] = *s_good;
     __syncthreads();
@@ -1286,13 +1297,15 @@ __device__ inline void load_partials(const double* __restrict__ part, const int*
     }
 }
 
-// The same with the canonical tree's first level (tile 2 p + tile 2 p + 1)
-// taken in the load: the two tiles of one sum are neighbours in the k-major
-// layout, so one 16-byte load brings both addends.  Lane p < 32 of wave w
-// takes the pair p of the wave's 64 tiles for sums 0..13, lane 32 + p the
-// same pair for sums 14..27: fourteen loads per lane instead of 28, each one
-// two contiguous 512-byte runs, and the level's selects and DPP moves go
-// (a + b == b + a bit for bit; a tile beyond n_tiles is the +0.0 it was).
+// The level scratch's loader, with the canonical tree's first level (tile 2 p
+// + tile 2 p + 1) taken in the load: the two tiles of one sum are neighbours,
+// so one 16-byte load brings both addends.  Lane p < 32 of wave w takes the
+// pair p of the wave's 64 tiles for sums 0..13, lane 32 + p the same pair for
+// sums 14..27: fourteen loads per lane instead of 28, and the level's selects
+// and DPP moves go (a + b == b + a bit for bit; a tile beyond n_tiles is the
+// +0.0 it was).  The PAIRED layout (partial_index) puts a wave's two halves
+// side by side, so each load instruction reads one contiguous 1 KB run (in
+// the k-major layout it was two 512-byte runs 14 * 2 KB apart).
 // a[14] feeds reduce_scatter_28_paired; gg stays tile t's count.
 __device__ inline void load_partials_paired(const double* __restrict__ part, const int* __restrict__ good,
                                             int n_tiles, double* a, int& gg) {
@@ -1300,11 +1313,11 @@ __device__ inline void load_partials_paired(const double* __restrict__ part, con
     const int t0 = (t & ~63) + 2 * (t & 31);
     if (t0 < n_tiles) {
         const bool has1 = t0 + 1 < n_tiles;
-        const double2* __restrict__ p2 =
-            reinterpret_cast<const double2*>(part + ((t & 32) ? (size_t)(kSums / 2) * kMaxTiles : 0) + t0);
+        // [k][w][h][j] with w = t >> 6, h = (t >> 5) & 1, j = 2 (t & 31): double 256 k + 2 t
+        const double2* __restrict__ p2 = reinterpret_cast<const double2*>(part) + t;
 #pragma unroll
         for (int k = 0; k < kSums / 2; ++k) {
-            const double2 x = p2[(size_t)k * (kMaxTiles / 2)];
+            const double2 x = p2[(size_t)k * kMaxTiles];
             a[k] = x.x + (has1 ? x.y : 0.0);
         }
     } else {
@@ -1644,9 +1657,10 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         double pose[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) pose[k] = s_pose[k];
-        direct_tile_pf<FAST>(a, fp, lv, pose, blockIdx.x, s_pf, merged, a.s.part + (size_t)lv * kMaxTiles * kSums,
-                       a.s.good + lv * kMaxTiles, s_pts, &s_good, &s_cnt, qt, src_lanes,
-                       SP ? &s_sp : nullptr);
+        direct_tile_pf<FAST, false, kWaves, true>(a, fp, lv, pose, blockIdx.x, s_pf, merged,
+                                                  a.s.part + (size_t)lv * kMaxTiles * kSums,
+                                                  a.s.good + lv * kMaxTiles, s_pts, &s_good, &s_cnt, qt,
+                                                  src_lanes, SP ? &s_sp : nullptr);
     }
 #ifdef VISO_PROBE
     // block 0 exit: its stamps to the launch's ring slot.  The exit stamp is
@@ -2117,6 +2131,36 @@ void launch_set_pose(double* dst, const double src[12], hipStream_t stream) {
     Pose12v p;
     for (int k = 0; k < 12; ++k) p.v[k] = src[k];
     set_pose_kernel<<<1, 64, 0, stream>>>(dst, p);
+}
+
+namespace {
+// Stage entry (viso_direct_solve): one wave runs the product's faithful solve
+// (solve_wave0, iteration 0) on given sums, nGood and T21; the level kernels'
+// solver wave starts from the same LDS words.
+__global__ __launch_bounds__(64) void direct_solve_kernel(const double* __restrict__ sums, int ngood,
+                                                          const double* __restrict__ state_in,
+                                                          double* __restrict__ stats, double* __restrict__ state_out) {
+    __shared__ SolveLds L;
+    const int lane = threadIdx.x;
+    if (lane < kSolveSums) L.S[lane] = sums[lane];
+    if (lane == 0) {
+        for (int k = 0; k < 7; ++k) L.state[k] = L.best[k] = state_in[k];
+        L.ngood = ngood;
+        L.cost = 0.0;
+        L.last_cost = 0.0;
+        L.cont = 0;
+    }
+    __syncthreads();
+    solve_wave0(L, 0, stats);
+    __syncthreads();
+    if (lane < 7) state_out[lane] = L.state[lane];
+}
+}  // namespace
+
+void launch_direct_solve(const double* sums28, int ngood, const double* state7, double* stats50, double* state_out7,
+                         hipStream_t stream) {
+    static_assert(kStats == 50, "viso_direct_solve's stats row");
+    direct_solve_kernel<<<1, 64, 0, stream>>>(sums28, ngood, state7, stats50, state_out7);
 }
 
 size_t direct_scratch_bytes() {

@@ -140,6 +140,61 @@ __device__ __attribute__((always_inline)) inline void solve_after_lu(SolveLds& L
                                                                       double h, int iter, double* stats,
                                                                       unsigned long long* stamps);
 
+// The row exchange of LU step K (rows K and p, p wave-uniform in K..5, whole
+// rows as Eigen's transposition) done where the rows live: one asm statement
+// per step that compares p and moves only the two rows' twelve doubles, its
+// operands tied ("+v").  To the compiler the statement is straight-line code
+// that keeps every element in its register, so no path pays a register copy
+// for the exchange (a C++ swap under `if (p == i)` turns each join into
+// copies of the matrix's register pairs on every path, the no-swap path
+// included).  p == K costs one compare and one branch.
+#define VISO_LU_X1(r, c)                                                        \
+    "v_mov_b64 %[t], %[a" #c "]\n\tv_mov_b64 %[a" #c "], %[" #r #c "]\n\t" \
+    "v_mov_b64 %[" #r #c "], %[t]\n\t"
+#define VISO_LU_XROW(r) \
+    VISO_LU_X1(r, 0) VISO_LU_X1(r, 1) VISO_LU_X1(r, 2) VISO_LU_X1(r, 3) VISO_LU_X1(r, 4) VISO_LU_X1(r, 5)
+#define VISO_LU_SKIP(k) "s_cmp_eq_u32 %[p], " #k "\n\ts_cbranch_scc1 9f\n\t"
+// rows up to the last: "is p this row? exchange, done"
+#define VISO_LU_CASE(i, lbl, r) \
+    "s_cmp_lg_u32 %[p], " #i "\n\ts_cbranch_scc1 " #lbl "f\n\t" VISO_LU_XROW(r) "s_branch 9f\n" #lbl ":\n\t"
+#define VISO_LU_END "9:"
+#define VISO_LU_ROW(n, r)                                                                              \
+    [n##0] "+v"(A[6 * (r) + 0]), [n##1] "+v"(A[6 * (r) + 1]), [n##2] "+v"(A[6 * (r) + 2]), \
+        [n##3] "+v"(A[6 * (r) + 3]), [n##4] "+v"(A[6 * (r) + 4]), [n##5] "+v"(A[6 * (r) + 5])
+template <int K>
+__device__ __attribute__((always_inline)) inline void lu_exchange(double* A, int p) {
+    double t;
+    if constexpr (K == 0)
+        asm(VISO_LU_SKIP(0) VISO_LU_CASE(1, 1, b) VISO_LU_CASE(2, 2, c) VISO_LU_CASE(3, 3, d) VISO_LU_CASE(4, 4, e)
+                VISO_LU_XROW(f) VISO_LU_END
+            : VISO_LU_ROW(a, 0), VISO_LU_ROW(b, 1), VISO_LU_ROW(c, 2), VISO_LU_ROW(d, 3), VISO_LU_ROW(e, 4),
+              VISO_LU_ROW(f, 5), [t] "=&v"(t)
+            : [p] "s"(p)
+            : "scc");
+    else if constexpr (K == 1)
+        asm(VISO_LU_SKIP(1) VISO_LU_CASE(2, 1, b) VISO_LU_CASE(3, 2, c) VISO_LU_CASE(4, 3, d) VISO_LU_XROW(e)
+                VISO_LU_END
+            : VISO_LU_ROW(a, 1), VISO_LU_ROW(b, 2), VISO_LU_ROW(c, 3), VISO_LU_ROW(d, 4), VISO_LU_ROW(e, 5),
+              [t] "=&v"(t)
+            : [p] "s"(p)
+            : "scc");
+    else if constexpr (K == 2)
+        asm(VISO_LU_SKIP(2) VISO_LU_CASE(3, 1, b) VISO_LU_CASE(4, 2, c) VISO_LU_XROW(d) VISO_LU_END
+            : VISO_LU_ROW(a, 2), VISO_LU_ROW(b, 3), VISO_LU_ROW(c, 4), VISO_LU_ROW(d, 5), [t] "=&v"(t)
+            : [p] "s"(p)
+            : "scc");
+    else if constexpr (K == 3)
+        asm(VISO_LU_SKIP(3) VISO_LU_CASE(4, 1, b) VISO_LU_XROW(c) VISO_LU_END
+            : VISO_LU_ROW(a, 3), VISO_LU_ROW(b, 4), VISO_LU_ROW(c, 5), [t] "=&v"(t)
+            : [p] "s"(p)
+            : "scc");
+    else if constexpr (K == 4)
+        asm(VISO_LU_SKIP(4) VISO_LU_XROW(b) VISO_LU_END
+            : VISO_LU_ROW(a, 4), VISO_LU_ROW(b, 5), [t] "=&v"(t)
+            : [p] "s"(p)
+            : "scc");
+}
+
 // One GN step of one level on wave 0 (all 64 lanes): L.S -> update, the new
 // L.state and the loop decision L.cont (src/viso.cpp:731-753), with the LU
 // replicated in every lane's registers (the
@@ -155,7 +210,8 @@ __device__ __attribute__((always_inline)) inline void solve_wave0_rep(SolveLds& 
     const double h = in ? L.S[r0 * 6 - (r0 * (r0 - 1)) / 2 + (c0 - r0)] : 0.0;
     // ---- Eigen PartialPivLU (first maximal |pivot| wins), replicated in the
     // registers of every lane: no cross-lane traffic on the serial chain; the
-    // pivot row is wave-uniform, so a row swap is a scalar branch + moves.
+    // pivot row is wave-uniform, so a row exchange is a scalar compare and, if
+    // taken, the two rows' moves (lu_exchange).
     double A[36];
     int tr[6];
 #ifdef VISO_LU_TWICE
@@ -165,12 +221,19 @@ __device__ __attribute__((always_inline)) inline void solve_wave0_rep(SolveLds& 
 #pragma clang loop unroll(disable)
     for (int rep = 0; rep < 2; ++rep) {
 #endif
+    // the lower triangle is read through an offset the compiler cannot see
+    // (0): its loads stay apart from the upper triangle's, so A[r][c] and
+    // A[c][r] start in registers of their own (one shared register has to be
+    // copied apart on every path before step 0's tied exchange)
+    int lower = 0;
+    asm("" : "+v"(lower));
+    const double* SL = L.S + lower;
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             const int r1 = r < c ? r : c, c1 = r < c ? c : r;
-            A[6 * r + c] = L.S[r1 * 6 - (r1 * (r1 - 1)) / 2 + (c1 - r1)];
+            A[6 * r + c] = (r > c ? SL : L.S)[r1 * 6 - (r1 * (r1 - 1)) / 2 + (c1 - r1)];
         }
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -187,16 +250,13 @@ __device__ __attribute__((always_inline)) inline void solve_wave0_rep(SolveLds& 
         p = __builtin_amdgcn_readfirstlane(p);
         tr[k] = p;
         if (__builtin_amdgcn_readfirstlane(best != 0.0 ? 1 : 0)) {
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) {
-                if (p == i) {
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        const double tmp = A[6 * k + c];
-                        A[6 * k + c] = A[6 * i + c];
-                        A[6 * i + c] = tmp;
-                    }
-                }
+            switch (k) {  // k is a constant of the unrolled loop
+                case 0: lu_exchange<0>(A, p); break;
+                case 1: lu_exchange<1>(A, p); break;
+                case 2: lu_exchange<2>(A, p); break;
+                case 3: lu_exchange<3>(A, p); break;
+                case 4: lu_exchange<4>(A, p); break;
+                default: break;
             }
             const double piv = A[7 * k];
             if (QL && k < 4) {

@@ -409,7 +409,7 @@ constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of
 // direct_scratch_bytes() by direct_scratch_at).
 struct DirectScratch {
-    double* part = nullptr;       // [kLevels][256 tiles][28] tile partial sums
+    double* part = nullptr;       // [kLevels][14][4][2][64] tile partial sums (direct.hip partial_index)
     int* good = nullptr;          // [kLevels][256]
     double* state = nullptr;      // [kLevels + 1][8] T21 per level (+ result)
     double* cont_part = nullptr;  // [256 workgroups][256][28] continuation scratch
@@ -432,6 +432,12 @@ void launch_direct_pose(const FrameDev& last, const FrameDev& cur, const PyrGeom
                         const DirectScratch& s, double* stats, double* pose_out, double* log,
                         int log_index, hipStream_t stream, int precision = VISO_PRECISION_FAITHFUL,
                         bool scalar_pass = true);
+// One faithful Gauss-Newton solve of a level (iteration 0) on one wave, as the
+// level kernels' solver runs it: sums28 = the 21 upper-triangle sums of H,
+// b (6), the cost sum; state7 = T21 (quaternion xyzw, t).  Device pointers.
+// stats50 = [nGood, cost, H(36), b(6), update(6)]; state_out7 = the new T21.
+void launch_direct_solve(const double* sums28, int ngood, const double* state7, double* stats50,
+                         double* state_out7, hipStream_t stream);
 // The same call split for the frame pipeline: L(3..0) of this frame, then F
 // later.  With `merge`, L(3) also runs the previous frame's pending F (its
 // level-0 solve; the solved pose is this frame's `last` pose and seed, so
