@@ -320,7 +320,8 @@ int viso_direct_pose(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_py
         VISO_HIP_CHECK(hipMemcpyAsync(base + o_p, points, 24 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_pl, pose_last, 96, hipMemcpyHostToDevice, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_pio, pose_io, 96, hipMemcpyHostToDevice, c->stream));
-    const double K[4] = {c->p.fx, c->p.fy, c->p.cx, c->p.cy};
+    double K[4];
+    c->intrinsics(K);
     {
         TimedRegion t(c->timing, VISO_KERNEL_DIRECT, c->stream);
         launch_direct_pose(frame_from_base((const uint8_t*)(base + o_l), g),
@@ -399,10 +400,7 @@ static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_
     a.out_stride = 0;
     a.points = (const double*)(base + o_p);
     a.n = n;
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.thresh = c->p.photometric_error_thresh;
     for (int l = 0; l < kLevels; ++l) {
         a.g.w[l] = g.w[l];
@@ -523,7 +521,8 @@ extern "C" int viso_photometric_ba(viso_ctx* c, const uint8_t* const* kf_images,
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_pose, kf_poses, 96 * (size_t)n_kf, hipMemcpyHostToDevice, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_pts, points, 24 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_host, host, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const double K[4] = {c->p.fx, c->p.fy, c->p.cx, c->p.cy};
+    double K[4];
+    c->intrinsics(K);
     if (launch_photometric_ba(l0, n_kf, w, h, K, (double*)(base + o_pose), (double*)(base + o_pts),
                               (const int*)(base + o_host), n, iterations, c->ba_scratch.ptr,
                               (double*)(base + o_rep), c->stream))

@@ -169,6 +169,13 @@ constexpr int kLkRing = 64;
 
 struct viso_ctx {
     viso_params p{};
+    // fx, fy, cx, cy: the K[4] of every kernel argument block
+    void intrinsics(double K[4]) const {
+        K[0] = p.fx;
+        K[1] = p.fy;
+        K[2] = p.cx;
+        K[3] = p.cy;
+    }
     int device = 0;
     hipStream_t stream = nullptr;
     viso::PyrGeom geom{};
@@ -360,6 +367,14 @@ struct viso_ctx {
     viso::DevBuf mapwin_buf;
     // *retired = false: nothing would be kept, map and keyframes unchanged
     int retire_keyframe(int cur, bool* retired);
+    // A map rewrite (retirement, cull, promotion) changes map_pts in place and
+    // rebuilds the LK templates.  Entry: the context stream is ordered behind
+    // every reader on lk_stream (its last batch; a chunk's resident grid) and
+    // the background work; upload_hosts: point_host goes to point_host_dev.
+    // Exit: the kept compacted points (with rec, their track records) are
+    // copied over the map; point_host = the first kept of hosts, n_map = kept.
+    int begin_map_rewrite(bool upload_hosts);
+    int end_map_rewrite(const double* pts, const void* rec, const std::vector<int32_t>& hosts, int kept);
     // pose refinement (viso_set_pose_refine; refine.hip): every tracking
     // frame's pose is refined on its own LK row — its final solve and its LK
     // alignment (a batch of one) run at once on the context stream, then one

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_rank.hpp"
 #include "context.hpp"
 #include "device_math.hpp"
 
@@ -31,7 +32,6 @@ namespace {
 constexpr double kInf = __builtin_huge_val();
 
 __device__ inline bool uni(bool b) { return __builtin_amdgcn_readfirstlane(b ? 1 : 0) != 0; }
-__device__ inline bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // min over the wave (exact in any order)
 __device__ inline double wave_min(double v) {
@@ -41,22 +41,6 @@ __device__ inline double wave_min(double v) {
         v = o < v ? o : v;
     }
     return v;
-}
-
-// a camera point through pose (R row-major + t) and K as project_px does;
-// returns its depth
-__device__ inline double seed_project(const double* pose, const Intrinsics& K, const double* W, double& u,
-                                      double& v) {
-    double c[3];
-    mat3_vec(pose, W, c);
-    c[0] = c[0] + pose[9];
-    c[1] = c[1] + pose[10];
-    c[2] = c[2] + pose[11];
-    const double z = c[2];
-    const double x = c[0] / z, y = c[1] / z;
-    u = x * K.fx + K.cx;
-    v = y * K.fy + K.cy;
-    return z;
 }
 
 __global__ __launch_bounds__(256) void seed_update_kernel(SeedUpdateArgs a) {
@@ -79,14 +63,7 @@ __global__ __launch_bounds__(256) void seed_update_kernel(SeedUpdateArgs a) {
     do {
         // 1. the segment: R = R_c R_h^T, t = t_c - R t_h, q = R f
         double R[9], t[3], q[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                R[3 * r + c] = (cp[3 * r] * hp[3 * c] + cp[3 * r + 1] * hp[3 * c + 1]) + cp[3 * r + 2] * hp[3 * c + 2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            t[r] = cp[9 + r] - ((R[3 * r] * hp[9] + R[3 * r + 1] * hp[10]) + R[3 * r + 2] * hp[11]);
+        relative_motion(hp, cp, R, t);
         // f's two divisions on lanes 0 and 1
         const double fq = ((odd ? v : u) - (odd ? K.cy : K.cx)) / (odd ? K.fy : K.fx);
         const double f0 = readlane_f64(fq, 0), f1 = readlane_f64(fq, 1);
@@ -137,19 +114,18 @@ __global__ __launch_bounds__(256) void seed_update_kernel(SeedUpdateArgs a) {
         // lanes Qv (lk_warp_kernel's arrangement).
         const double za = 1.0 / mu;
         const double qu = odd ? u : u + 4.0, qv = odd ? v + 4.0 : v;
-        const double d[3] = {(qu - K.cx) / K.fx * za - hp[9], (qv - K.cy) / K.fy * za - hp[10], za - hp[11]};
+        const double Ph[3] = {(qu - K.cx) / K.fx * za, (qv - K.cy) / K.fy * za, za};
         double Wp[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Wp[j] = (hp[j] * d[0] + hp[3 + j] * d[1]) + hp[6 + j] * d[2];
+        camera_to_world(hp, Ph, Wp);
         double uq, vq;
-        const double zq = seed_project(cp, K, Wp, uq, vq);
+        const double zq = project_px_depth(cp, K, Wp, uq, vq);
         const double au = (uq - mx) / 4.0, av = (vq - my) / 4.0;
         const double A00 = readlane_f64(au, 0), A10 = readlane_f64(av, 0);
         const double A01 = readlane_f64(au, 1), A11 = readlane_f64(av, 1);
         const double zu = readlane_f64(zq, 0), zv = readlane_f64(zq, 1);
         const double det = A00 * A11 - A01 * A10;
         double D = fabs(det);
-        if (!uni(za > 0 && zu > 0 && zv > 0 && finite_d(A00) && finite_d(A01) && finite_d(A10) && finite_d(A11) &&
+        if (!uni(za > 0 && zu > 0 && zv > 0 && finite_f64(A00) && finite_f64(A01) && finite_f64(A10) && finite_f64(A11) &&
                  1.0 / kSeedAreaRatio <= D && D <= kSeedAreaRatio)) {
             st = 2;
             break;
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(256) void seed_update_kernel(SeedUpdateArgs a) {
         const double n_k = (mm - c_k) / f_k;
         const double rq = (n_k * q[2] - q_k) / (t_k - n_k * t[2]);
         const double robs = readlane_f64(rq, 0), r1 = readlane_f64(rq, 1);
-        if (!uni(finite_d(robs) && finite_d(r1) && rho_min <= robs && robs <= rho_max)) {
+        if (!uni(finite_f64(robs) && finite_f64(r1) && rho_min <= robs && robs <= rho_max)) {
             st = 9;
             break;
         }
@@ -267,20 +243,15 @@ __global__ __launch_bounds__(256) void seed_update_kernel(SeedUpdateArgs a) {
     }
 }
 
-__device__ inline int popc_below(unsigned long long ballot, int lane) {
-    return __popcll(ballot & ((1ULL << lane) - 1ULL));
-}
-
 // Promotion: one workgroup walks the seeds in chunks of 1024.  Per seed a
 // class (converged first, then dropped); the converged ones of rank < room
 // become points in seed order, every seed that is neither promoted nor dropped
 // is kept, compacted in place in seed order (a chunk's rows are all read
-// before its first barrier and written behind it, to indices no later chunk
-// reads).  Prefixes by ballot / popcount and a 16-entry table, as
-// mono_compact_kernel.
+// before the first block_rank call and written behind the second, to indices
+// no later chunk reads; block_rank.hpp).
 __global__ __launch_bounds__(1024) void seed_promote_kernel(SeedPromoteArgs a) {
-    __shared__ int s_c[16], s_s[16], s_d[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_w[2 * 16], s_s[16];
+    const int tid = threadIdx.x;
     int base_c = 0, base_s = 0, base_d = 0;
     for (int i0 = 0; i0 < a.n; i0 += 1024) {
         const int i = i0 + tid;
@@ -299,43 +270,21 @@ __global__ __launch_bounds__(1024) void seed_promote_kernel(SeedPromoteArgs a) {
         const double lim = a.conv_rel * mu;
         const bool conv = live && cnt.x >= a.min_good && s2 <= lim * lim;
         const bool drop = live && !conv && (cnt.y >= a.max_bad || cnt.z >= a.max_lost);
-        const unsigned long long bc = __ballot(conv), bd = __ballot(drop);
-        if (lane == 0) {
-            s_c[wave] = __popcll(bc);
-            s_d[wave] = __popcll(bd);
-        }
-        __syncthreads();
-        int wc = 0, tc = 0, td = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            wc += k < wave ? s_c[k] : 0;
-            tc += s_c[k];
-            td += s_d[k];
-        }
-        const int rank = base_c + wc + popc_below(bc, lane);
+        const bool cd[2] = {conv, drop};
+        BlockRank r[2];  // (of the dropped only the count)
+        block_rank<16>(cd, s_w, r);
+        const int rank = base_c + r[0].rank;
         const bool prom = conv && rank < a.room;
         const bool surv = live && !prom && !drop;
-        const unsigned long long bs = __ballot(surv);
-        if (lane == 0) s_s[wave] = __popcll(bs);
-        __syncthreads();
-        int wsv = 0, ts = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            wsv += k < wave ? s_s[k] : 0;
-            ts += s_s[k];
-        }
-        __syncthreads();
+        const BlockRank rs = block_rank<16>(surv, s_s);
         if (prom) {
             // R_h^T (f / mu - t_h)
-            const double* hp = a.kf_poses + 12 * h;
-            const double d0 = ((u - a.K[2]) / a.K[0]) / mu - hp[9], d1 = ((v - a.K[3]) / a.K[1]) / mu - hp[10],
-                         d2 = 1.0 / mu - hp[11];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a.out_pts[3 * (size_t)rank + j] = (hp[j] * d0 + hp[3 + j] * d1) + hp[6 + j] * d2;
+            const double Ph[3] = {((u - a.K[2]) / a.K[0]) / mu, ((v - a.K[3]) / a.K[1]) / mu, 1.0 / mu};
+            camera_to_world(a.kf_poses + 12 * h, Ph, a.out_pts + 3 * (size_t)rank);
             a.out_host[rank] = h;
         }
         if (surv) {
-            const int j = base_s + wsv + popc_below(bs, lane);
+            const int j = base_s + rs.rank;
             a.rows.h[j] = h;
             a.rows.uv[2 * (size_t)j] = u;
             a.rows.uv[2 * (size_t)j + 1] = v;
@@ -343,9 +292,9 @@ __global__ __launch_bounds__(1024) void seed_promote_kernel(SeedPromoteArgs a) {
             a.rows.s2[j] = s2;
             a.rows.cnt[j] = cnt;
         }
-        base_c += tc;
-        base_s += ts;
-        base_d += td;
+        base_c += r[0].total;
+        base_s += rs.total;
+        base_d += r[1].total;
     }
     if (tid == 0) {
         a.counts[0] = base_c;
@@ -360,7 +309,7 @@ __global__ __launch_bounds__(1024) void seed_promote_kernel(SeedPromoteArgs a) {
 // counts[0] = survivors
 __global__ __launch_bounds__(1024) void seed_retire_kernel(SeedRows rows, int n, int* counts) {
     __shared__ int s_s[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
@@ -376,18 +325,9 @@ __global__ __launch_bounds__(1024) void seed_retire_kernel(SeedRows rows, int n,
             cnt = rows.cnt[i];
         }
         const bool keep = i < n && h > 0;
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) s_s[wave] = __popcll(b);
-        __syncthreads();
-        int wb = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            wb += k < wave ? s_s[k] : 0;
-            tot += s_s[k];
-        }
-        __syncthreads();
+        const BlockRank r = block_rank<16>(keep, s_s);
         if (keep) {
-            const int j = base + wb + popc_below(b, lane);
+            const int j = base + r.rank;
             rows.h[j] = h - 1;
             rows.uv[2 * (size_t)j] = u;
             rows.uv[2 * (size_t)j + 1] = v;
@@ -395,7 +335,7 @@ __global__ __launch_bounds__(1024) void seed_retire_kernel(SeedRows rows, int n,
             rows.s2[j] = s2;
             rows.cnt[j] = cnt;
         }
-        base += tot;
+        base += r.total;
     }
     if (tid == 0) counts[0] = base;
 }
@@ -490,10 +430,7 @@ using namespace viso;
 // cell winners in corner order (a.win_xy, a.counts[1]).
 int viso_ctx::seed_candidates(MonoKfArgs& a, const uint8_t* level0, const PyrGeom& g, FastScratch& fs,
                               const double* pose_c, const double* points, int n_points) {
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     for (int k = 0; k < 9; ++k) a.Kinv[k] = Kinv[k];
     a.pose_c = pose_c;
     a.pose_k = pose_c;  // (the compaction's KLT seed is not used)
@@ -560,10 +497,7 @@ int viso_ctx::update_seeds(int cur) {
         a.g.w[l] = geom.w[l];
         a.g.h[l] = geom.h[l];
     }
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.p.max_steps = seed_max_steps;
     a.p.rho_min = 1.0 / seed_dmax;
     a.p.rho_max = 1.0 / seed_dmin;
@@ -584,23 +518,19 @@ int viso_ctx::update_seeds(int cur) {
 // One promotion (on_new_frame, behind the frame's update and the point
 // refinement, ahead of the cull and the insertion check).  The promoted points
 // go straight behind the map.  One host sync for the counts; a promotion that
-// appended points reads their hosts back too and rebuilds the LK templates,
-// so the context stream is first ordered behind every reader on lk_stream, as
-// a cull (pointcull.hip).
+// appended points reads their hosts back too and rebuilds the LK templates:
+// a map rewrite's entry (begin_map_rewrite, mapwin.hip; the hosts are not
+// read on the device, so none are uploaded).
 int viso_ctx::promote_seeds() {
     if (!seeds_on() || n_seeds <= 0) return VISO_OK;
     if ((int)point_host.size() != n_map) return VISO_ERR_STATE;
     const int room = std::min(kMaxMapPoints - n_map, n_seeds);
-    if (int rc = order_after_lk(lk_seq - 1, stream)) return rc;
-    if (bg_done) VISO_HIP_CHECK(hipStreamWaitEvent(stream, bg_done, 0));
+    if (int rc = begin_map_rewrite(false)) return rc;
     SeedPromoteArgs a{};
     a.rows = seed_rows();
     a.n = n_seeds;
     a.kf_poses = (const double*)kf_poses.ptr;
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.min_good = seed_min_good;
     a.conv_rel = seed_conv_rel;
     a.max_bad = seed_max_bad;
@@ -848,10 +778,7 @@ int viso_depth_seeds_update(viso_ctx* c, const uint8_t* kf_pyrs, const double* k
         a.g.w[l] = g.w[l];
         a.g.h[l] = g.h[l];
     }
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.p.max_steps = max_steps;
     a.p.rho_min = 1.0 / depth_max;
     a.p.rho_max = 1.0 / depth_min;
@@ -906,10 +833,7 @@ int viso_depth_seeds_promote(viso_ctx* c, const double* kf_poses, int32_t n_kf, 
     }
     a.n = n;
     a.kf_poses = (const double*)(base + o_kp);
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.min_good = min_good;
     a.conv_rel = conv_rel;
     a.max_bad = max_bad;

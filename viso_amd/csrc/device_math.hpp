@@ -48,6 +48,76 @@ __device__ inline bool inside_px(double u, double v, int w, int h) {
     return u >= 0 && u < w && v >= 0 && v < h;
 }
 
+// The two pixel forms differ in their last bits and each has its restatements:
+// project_px and project_px_depth divide first, (x / z) * fx + cx;
+// pixel_mul_first multiplies first, K[0] * x / z + K[2] (tests/mono_kf_ref.py,
+// map_window_ref.py, point_cull_ref.py).
+
+// project_px at level 0 that also returns the point's depth in `pose`
+__device__ inline double project_px_depth(const double* pose, const Intrinsics& K, const double* W, double& u,
+                                          double& v) {
+    double c[3];
+    mat3_vec(pose, W, c);
+    c[0] = c[0] + pose[9];
+    c[1] = c[1] + pose[10];
+    c[2] = c[2] + pose[11];
+    const double z = c[2];
+    const double x = c[0] / z, y = c[1] / z;
+    u = x * K.fx + K.cx;
+    v = y * K.fy + K.cy;
+    return z;
+}
+
+// the pixel of camera point (x, y, z), multiplying first; K = fx, fy, cx, cy
+__device__ inline void pixel_mul_first(const double* K, double x, double y, double z, double& u, double& v) {
+    u = K[0] * x / z + K[2];
+    v = K[1] * y / z + K[3];
+}
+
+// The cell (cy * ncx + cx) of the grid a.{w, h, cell, ncx, ncy} that `pose`
+// sees P in through a.K (pixel_mul_first), or -1: P in front of the camera
+// and inside the image.  Args: MapWinArgs, MonoKfArgs.
+template <class Args>
+__device__ inline int seen_cell(const Args& a, const double* __restrict__ pose, const double* __restrict__ P) {
+    double Pc[3];
+    mat3_vec(pose, P, Pc);
+    Pc[0] = Pc[0] + pose[9];
+    Pc[1] = Pc[1] + pose[10];
+    Pc[2] = Pc[2] + pose[11];
+    if (!(Pc[2] > 0)) return -1;
+    double u, v;
+    pixel_mul_first(a.K, Pc[0], Pc[1], Pc[2], u, v);
+    if (!(u >= 0 && u < a.w && v >= 0 && v < a.h)) return -1;
+    const int cx = (int)(u / a.cell), cy = (int)(v / a.cell);
+    if (cx < 0 || cx >= a.ncx || cy < 0 || cy >= a.ncy) return -1;
+    return cy * a.ncx + cx;
+}
+
+// neither an infinity nor a NaN
+__device__ inline bool finite_f64(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// Pw = R^T (Pc - t) of a Tcw pose (oracle_viso.cpp restates the same order)
+__device__ inline void camera_to_world(const double* pose, const double* Pc, double* Pw) {
+    const double d0 = Pc[0] - pose[9], d1 = Pc[1] - pose[10], d2 = Pc[2] - pose[11];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Pw[k] = (pose[k] * d0 + pose[3 + k] * d1) + pose[6 + k] * d2;
+}
+
+// The motion from frame b to frame a of two Tcw poses (Pc = R Pw + t):
+// R = R_a R_b^T, T = t_a - R t_b
+__device__ inline void relative_motion(const double* __restrict__ pb, const double* __restrict__ pa, double* R,
+                                       double* T) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            R[3 * i + j] = (pa[3 * i] * pb[3 * j] + pa[3 * i + 1] * pb[3 * j + 1]) + pa[3 * i + 2] * pb[3 * j + 2];
+    double Rt[3];
+    mat3_vec(R, pb + 9, Rt);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) T[r] = pa[9 + r] - Rt[r];
+}
+
 // ---------------------------------------------------------------- SE(3)
 struct SE3d {
     double q[4];  // x, y, z, w

@@ -138,10 +138,7 @@ int viso_ctx::init() {
         const double K[9] = {p.fx, 0, p.cx, 0, p.fy, p.cy, 0, 0, 1};
         eigen_inverse3(K, Kinv);
         for (int k = 0; k < 9; ++k) a.Kinv[k] = Kinv[k];
-        a.K[0] = p.fx;
-        a.K[1] = p.fy;
-        a.K[2] = p.cx;
-        a.K[3] = p.cy;
+        intrinsics(a.K);
         a.disparity_thresh = p.disparity_squared_thresh;
         a.proj_thresh = p.projection_error_thresh;
         a.parallax_thresh = p.parallax_thresh;
@@ -523,10 +520,7 @@ LkAlignArgs viso_ctx::lk_args() {
     a.kf_poses = (const double*)kf_poses.ptr;
     a.points = (const double*)map_pts.ptr;
     a.n = n_map;
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.thresh = p.photometric_error_thresh;
     for (int l = 0; l < kLevels; ++l) {
         a.g.w[l] = g.w[l];
@@ -764,7 +758,8 @@ int viso_ctx::flush_host_q() {
 
 int viso_ctx::resolve_direct() {
     if (!dpend) return VISO_OK;
-    const double K[4] = {p.fx, p.fy, p.cx, p.cy};
+    double K[4];
+    intrinsics(K);
     launch_direct_final(frame(dpend_last), frame(dpend_cur), geom, K, (const double*)map_pts.ptr,
                         n_map, pose_of(dpend_last), direct, (double*)direct_stats.ptr,
                         pose_of(dpend_cur), dpend_log >= 0 ? (double*)pose_log.ptr : nullptr,
@@ -1096,7 +1091,8 @@ int viso_ctx::bundle_adjust() {
                                   stream));
     const uint8_t* l0[kMaxKeyframes];
     for (int k = 0; k < nk; ++k) l0[k] = frame(kf_slots[(size_t)k]).l[0];
-    const double K[4] = {p.fx, p.fy, p.cx, p.cy};
+    double K[4];
+    intrinsics(K);
     if (launch_photometric_ba(l0, nk, geom.w[0], geom.h[0], K, (double*)kf_poses.ptr, (double*)map_pts.ptr,
                               (const int*)point_host_dev.ptr, n_map, ba_iterations, ba_scratch.ptr, nullptr,
                               stream))
@@ -1195,7 +1191,8 @@ int viso_ctx::on_new_frame(int cur) {
     // (written by the ingest's pyramid launch for its last frame, PyrOwn)
     if (state != VISO_STATE_RUNNING && cur != ident_slot) launch_set_pose(pose_of(cur), kIdentityPose, stream);
     if (cur == ident_slot) ident_slot = -1;
-    const double K[4] = {p.fx, p.fy, p.cx, p.cy};
+    double K[4];
+    intrinsics(K);
     bool counted = true;  // ++init_.frame_cnt at the end of kInitialization
     switch (state) {
         case VISO_STATE_INITIALIZATION: {

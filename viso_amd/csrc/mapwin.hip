@@ -13,41 +13,21 @@
 // the keyframe poses shifted down one row.
 //
 // Mapping: one lane per point in (1) and (2); (3) is one workgroup walking
-// the map 1024 points a round (wave prefixes by ballot, the workgroup's by a
-// 16-entry table).  Every count is formed on the device; the only atomics are
-// integer (a maximum per cell, three sums), so the result depends on nothing
-// but the data.  fp64 in the operand order of tests/map_window_ref.py,
+// the map 1024 points a round (block_rank.hpp).  Every count is formed on the
+// device; the only atomics are integer (a maximum per cell, three sums), so
+// the result depends on nothing but the data.  fp64 in the operand order of tests/map_window_ref.py,
 // -ffp-contract=off.
 #include <algorithm>
 #include <vector>
 
+#include "block_rank.hpp"
 #include "context.hpp"
+#include "device_math.hpp"
 #include "linalg.hpp"
 
 namespace viso {
 
 namespace {
-
-__device__ inline int popc_below(unsigned long long ballot, int lane) {
-    return __popcll(ballot & ((1ULL << lane) - 1ULL));
-}
-
-// the cell of c's grid that `pose` sees P in (cy * ncx + cx), or -1: P in
-// front of the camera and inside the image
-__device__ inline int seen_cell(const MapWinArgs& a, const double* __restrict__ pose, const double* __restrict__ P) {
-    double Pc[3];
-    mat3_vec(pose, P, Pc);
-    Pc[0] = Pc[0] + pose[9];
-    Pc[1] = Pc[1] + pose[10];
-    Pc[2] = Pc[2] + pose[11];
-    if (!(Pc[2] > 0)) return -1;
-    const double u = a.K[0] * Pc[0] / Pc[2] + a.K[2];
-    const double v = a.K[1] * Pc[1] / Pc[2] + a.K[3];
-    if (!(u >= 0 && u < a.w && v >= 0 && v < a.h)) return -1;
-    const int cx = (int)(u / a.cell), cy = (int)(v / a.cell);
-    if (cx < 0 || cx >= a.ncx || cy < 0 || cy >= a.ncy) return -1;
-    return cy * a.ncx + cx;
-}
 
 // (1) every point's cell in c; a live point marks it (every marking lane
 // stores the same value)
@@ -96,8 +76,8 @@ __global__ __launch_bounds__(256) void mapwin_claim_kernel(MapWinArgs a) {
 // survivors, counts[4] = kept; with something kept and shift_poses set,
 // keyframe pose row k + 1 moves to row k
 __global__ __launch_bounds__(1024) void mapwin_compact_kernel(MapWinArgs a) {
-    __shared__ int s_w[16], s_s[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_w[2 * 16];
+    const int tid = threadIdx.x;
     int base = 0, surv = 0;
     for (int i0 = 0; i0 < a.n; i0 += 1024) {
         const int i = i0 + tid;
@@ -113,30 +93,19 @@ __global__ __launch_bounds__(1024) void mapwin_compact_kernel(MapWinArgs a) {
             }
             a.keep[i] = f ? 1 : 0;
         }
-        const unsigned long long b = __ballot(f), bs = __ballot(s);
-        if (lane == 0) {
-            s_w[wave] = __popcll(b);
-            s_s[wave] = __popcll(bs);
-        }
-        __syncthreads();
-        int wb = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = s_w[k];
-            wb += k < wave ? t : 0;
-            tot += t;
-            surv += s_s[k];
-        }
-        __syncthreads();
+        const bool flags[2] = {f, s};
+        BlockRank r[2];  // (of the survivors only the count)
+        block_rank<16>(flags, s_w, r);
         if (f) {
-            const size_t j = (size_t)(base + wb + popc_below(b, lane));
+            const size_t j = (size_t)(base + r[0].rank);
             a.out_pts[3 * j] = a.pts[3 * (size_t)i];
             a.out_pts[3 * j + 1] = a.pts[3 * (size_t)i + 1];
             a.out_pts[3 * j + 2] = a.pts[3 * (size_t)i + 2];
             a.out_host[j] = nh;
             if (a.rec) a.out_rec[j] = a.rec[i];
         }
-        base += tot;
+        base += r[0].total;
+        surv += r[1].total;
     }
     if (tid == 0) {
         a.counts[3] = surv;
@@ -201,12 +170,31 @@ void launch_map_retire(const MapWinArgs& a, hipStream_t stream) {
 
 using namespace viso;
 
+int viso_ctx::begin_map_rewrite(bool upload_hosts) {
+    if (int rc = order_after_lk(lk_seq - 1, stream)) return rc;
+    if (bg_done) VISO_HIP_CHECK(hipStreamWaitEvent(stream, bg_done, 0));
+    if (upload_hosts && n_map > 0)
+        VISO_HIP_CHECK(hipMemcpyAsync(point_host_dev.ptr, point_host.data(), 4 * (size_t)n_map,
+                                      hipMemcpyHostToDevice, stream));
+    return VISO_OK;
+}
+
+int viso_ctx::end_map_rewrite(const double* pts, const void* rec, const std::vector<int32_t>& hosts, int kept) {
+    if (kept > 0) {
+        VISO_HIP_CHECK(hipMemcpyAsync(map_pts.ptr, pts, 24 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
+        if (rec)
+            VISO_HIP_CHECK(hipMemcpyAsync(pt_tracks.ptr, rec, 16 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
+    }
+    point_host.assign(hosts.begin(), hosts.begin() + kept);
+    n_map = kept;
+    return VISO_OK;
+}
+
 // One retirement in the frame path (on_new_frame's insertion check, ahead of
 // the check's insertion; cur's pose is final and every earlier LK batch has
 // been launched: finish_call).  The cull rewrites map_pts and kf_poses in
-// place and the LK templates are rebuilt behind it, so the context stream is
-// first ordered behind every reader on lk_stream (its last batch; a chunk's
-// resident grid).  Two read-backs in one host sync: the counts and the new
+// place and the LK templates are rebuilt behind it: a map rewrite
+// (begin_map_rewrite).  Two read-backs in one host sync: the counts and the new
 // hosts.  *retired = false: nothing would be kept, map and keyframes are
 // unchanged.
 int viso_ctx::retire_keyframe(int cur, bool* retired) {
@@ -217,14 +205,10 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     int rc = mapwin_buf.ensure(map_window_scratch_bytes(g.w[0], g.h[0], win_cell, kMaxMapPoints));
     if (!rc) rc = point_host_dev.ensure(4 * (size_t)kMaxMapPoints);
     if (rc) return rc;
-    if (int r2 = order_after_lk(lk_seq - 1, stream)) return r2;
-    if (bg_done) VISO_HIP_CHECK(hipStreamWaitEvent(stream, bg_done, 0));
+    if (int r2 = begin_map_rewrite(true)) return r2;
     MapWinArgs a{};
     map_window_scratch_at(a, mapwin_buf.ptr, g.w[0], g.h[0], win_cell, kMaxMapPoints);
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.pose_c = pose_of(cur);
     a.kf_poses = (double*)kf_poses.ptr;
     a.n_kf = nk;
@@ -233,9 +217,6 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     a.host = (const int*)point_host_dev.ptr;
     a.n = n;
     a.rec = cull_on() ? (const int4*)pt_tracks.ptr : nullptr;  // (viso_set_point_cull: a kept point's record moves with it)
-    if (n > 0)
-        VISO_HIP_CHECK(hipMemcpyAsync(point_host_dev.ptr, point_host.data(), 4 * (size_t)n, hipMemcpyHostToDevice,
-                                      stream));
     {
         TimedRegion t(timing, VISO_KERNEL_MAPWIN, stream);
         launch_map_retire(a, stream);
@@ -248,11 +229,7 @@ int viso_ctx::retire_keyframe(int cur, bool* retired) {
     VISO_HIP_CHECK(hipStreamSynchronize(stream));
     const int kept = std::max(0, std::min(h_int[12], n));
     if (kept == 0) return VISO_OK;
-    VISO_HIP_CHECK(hipMemcpyAsync(map_pts.ptr, a.out_pts, 24 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
-    if (a.rec)
-        VISO_HIP_CHECK(hipMemcpyAsync(pt_tracks.ptr, a.out_rec, 16 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
-    point_host.assign(hosts.begin(), hosts.begin() + kept);
-    n_map = kept;
+    if (int r2 = end_map_rewrite(a.out_pts, a.rec ? a.out_rec : nullptr, hosts, kept)) return r2;
     // the slot's readers on lk_stream are its lk_use batch, those on the
     // context stream end with this call's epoch: acquire_slot / wait_freed
     // order its reuse behind both
@@ -335,10 +312,7 @@ int viso_map_retire(viso_ctx* c, int32_t width, int32_t height, const double pos
     }
     MapWinArgs a{};
     map_window_scratch_at(a, c->scratch_c.ptr, width, height, cell, n);
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.pose_c = (const double*)(base + o_pc);
     a.kf_poses = (double*)(base + o_pk);
     a.n_kf = n_kf;

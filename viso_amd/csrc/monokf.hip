@@ -22,7 +22,9 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_rank.hpp"
 #include "context.hpp"
+#include "device_math.hpp"
 #include "linalg.hpp"
 
 namespace viso {
@@ -30,24 +32,6 @@ namespace viso {
 namespace {
 
 constexpr unsigned long long kCellMarked = ~0ULL;
-
-__device__ inline int popc_below(unsigned long long ballot, int lane) {
-    return __popcll(ballot & ((1ULL << lane) - 1ULL));
-}
-
-// R_kc = R_k R_c^T, T_kc = t_k - R_kc t_c (poses Tcw: Pc = R Pw + t)
-__device__ inline void relative_motion(const double* __restrict__ pc, const double* __restrict__ pk, double* R,
-                                       double* T) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            R[3 * i + j] = (pk[3 * i] * pc[3 * j] + pk[3 * i + 1] * pc[3 * j + 1]) + pk[3 * i + 2] * pc[3 * j + 2];
-    double Rt[3];
-    mat3_vec(R, pc + 9, Rt);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) T[r] = pk[9 + r] - Rt[r];
-}
 
 // K^-1 [x, y, 1] from the float keypoint (src/viso.cpp:46-47)
 __device__ inline void normalise_px(const double* Ki, float2 kp, double* x) {
@@ -61,19 +45,8 @@ __device__ inline void normalise_px(const double* Ki, float2 kp, double* x) {
 __global__ __launch_bounds__(256) void mono_occupancy_kernel(MonoKfArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n_map) return;
-    const double* P = a.map_pts + 3 * (size_t)i;
-    double Pc[3];
-    mat3_vec(a.pose_c, P, Pc);
-    Pc[0] = Pc[0] + a.pose_c[9];
-    Pc[1] = Pc[1] + a.pose_c[10];
-    Pc[2] = Pc[2] + a.pose_c[11];
-    if (!(Pc[2] > 0)) return;
-    const double u = a.K[0] * Pc[0] / Pc[2] + a.K[2];
-    const double v = a.K[1] * Pc[1] / Pc[2] + a.K[3];
-    if (!(u >= 0 && u < a.w && v >= 0 && v < a.h)) return;
-    const int cx = (int)(u / a.cell), cy = (int)(v / a.cell);
-    if (cx < 0 || cx >= a.ncx || cy < 0 || cy >= a.ncy) return;
-    a.cell_key[cy * a.ncx + cx] = kCellMarked;
+    const int cell = seen_cell(a, a.pose_c, a.map_pts + 3 * (size_t)i);
+    if (cell >= 0) a.cell_key[cell] = kCellMarked;
 }
 
 __device__ inline int corner_cell(const MonoKfArgs& a, const int4& c) {
@@ -97,12 +70,12 @@ __global__ __launch_bounds__(256) void mono_cell_winner_kernel(MonoKfArgs a) {
     atomicMax(a.cell_key + cell, corner_key(c, i));
 }
 
-// (2b) winners compacted in corner order (one workgroup; wave prefixes by
-// ballot, the workgroup's by a 16-entry table), with the KLT seed: the
-// rotation-only warp of the corner into k
+// (2b) winners compacted in corner order (one workgroup, block_rank.hpp),
+// with the KLT seed: the rotation-only warp of the corner into k (R_kc = R_k
+// R_c^T, T_kc = t_k - R_kc t_c)
 __global__ __launch_bounds__(1024) void mono_compact_kernel(MonoKfArgs a) {
     __shared__ int s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int n = min(*a.n_corners, a.cap_corners);
     double R[9], T[3];
     relative_motion(a.pose_c, a.pose_k, R, T);
@@ -116,28 +89,20 @@ __global__ __launch_bounds__(1024) void mono_compact_kernel(MonoKfArgs a) {
             const int cell = corner_cell(a, c);
             f = cell >= 0 && a.cell_key[cell] == corner_key(c, i);
         }
-        const unsigned long long b = __ballot(f);
-        if (lane == 0) s_w[wave] = __popcll(b);
-        __syncthreads();
-        int wb = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = s_w[k];
-            wb += k < wave ? t : 0;
-            tot += t;
-        }
-        __syncthreads();
-        const int j = base + wb + popc_below(b, lane);
+        const BlockRank r = block_rank<16>(f, s_w);
+        const int j = base + r.rank;
         if (f && j < a.cap_win) {
             const float2 k1 = make_float2((float)c.x, (float)c.y);
             double x1[3], q[3];
             normalise_px(a.Kinv, k1, x1);
             mat3_vec(R, x1, q);
+            double u, v;
+            pixel_mul_first(a.K, q[0], q[1], q[2], u, v);
             a.kp1[j] = k1;
-            a.kp2[j] = make_float2((float)(a.K[0] * q[0] / q[2] + a.K[2]), (float)(a.K[1] * q[1] / q[2] + a.K[3]));
+            a.kp2[j] = make_float2((float)u, (float)v);
             a.win_xy[j] = make_int2(c.x, c.y);
         }
-        base += tot;
+        base += r.total;
     }
     if (tid == 0) {
         a.counts[0] = n;
@@ -203,37 +168,27 @@ __global__ __launch_bounds__(256) void mono_triangulate_kernel(MonoKfArgs a) {
 }
 
 // (4b) accepted points in candidate order: a wave's offset is the sum of the
-// counts of the waves before it (integers: any order), a lane's its ballot
-// prefix; the last workgroup stores the total
+// counts of the waves before it (integers: any order), a lane's its rank in
+// the workgroup (block_rank.hpp); the last workgroup stores the total
 __global__ __launch_bounds__(256) void mono_emit_kernel(MonoKfArgs a) {
     __shared__ int s_sum[4], s_w[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * 256 + tid;
     const bool ok = i < a.cap_win && a.accept[i] != 0;
-    const unsigned long long b = __ballot(ok);
     int acc = 0;
     for (int k = tid; k < (int)blockIdx.x * 4; k += 256) acc += a.wave_cnt[k];
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) {
-        s_sum[wave] = acc;
-        s_w[wave] = __popcll(b);
-    }
-    __syncthreads();
-    int base = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-    int tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        base += k < wave ? s_w[k] : 0;
-        tot += s_w[k];
-    }
-    const int j = base + popc_below(b, lane);
+    if (lane == 0) s_sum[wave] = acc;
+    const BlockRank r = block_rank<4>(ok, s_w);  // (its first barrier publishes s_sum too)
+    const int before = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+    const int j = before + r.rank;
     if (ok && j < a.out_cap) {
         a.out[3 * (size_t)j] = a.cand_pts[3 * (size_t)i];
         a.out[3 * (size_t)j + 1] = a.cand_pts[3 * (size_t)i + 1];
         a.out[3 * (size_t)j + 2] = a.cand_pts[3 * (size_t)i + 2];
     }
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) a.counts[3] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]) + tot;
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) a.counts[3] = before + r.total;
 }
 
 }  // namespace
@@ -299,10 +254,7 @@ using namespace viso;
 int viso_ctx::mono_launch(MonoKfArgs& a, const FrameDev& fc, const FrameDev& fk, const PyrGeom& g, FastScratch& fs,
                           const double* pose_c, const double* pose_k, const double* points, int n_points, int cell,
                           double min_parallax_deg, double* out, int out_cap) {
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     for (int k = 0; k < 9; ++k) a.Kinv[k] = Kinv[k];
     a.proj_thresh = p.projection_error_thresh;
     a.cos_thresh = std::cos(min_parallax_deg * 3.14159265358979323846 / 180.0);

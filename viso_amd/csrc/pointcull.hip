@@ -17,25 +17,22 @@
 // Mapping: the update is one lane per point, the record one 16-byte load and
 // one 16-byte store.  The cull is one workgroup walking the map 1024 points a
 // round, twice: the candidates are counted (the abandonment is decided on the
-// device), then keep flags and the stable compaction (wave prefixes by
-// ballot, the workgroup's by a 16-entry table; the scheme of
-// mapwin_compact_kernel).  The only atomics are integer (three sums and a
+// device), then keep flags and the stable compaction (block_rank.hpp).  The
+// only atomics are integer (three sums and a
 // maximum), so the result depends on nothing but the data.  fp64 in the
 // operand order of tests/point_cull_ref.py, -ffp-contract=off.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "block_rank.hpp"
 #include "context.hpp"
+#include "device_math.hpp"
 #include "linalg.hpp"
 
 namespace viso {
 
 namespace {
-
-__device__ inline int popc_below(unsigned long long ballot, int lane) {
-    return __popcll(ballot & ((1ULL << lane) - 1ULL));
-}
 
 __global__ __launch_bounds__(256) void point_tracks_kernel(PointCullArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -54,8 +51,10 @@ __global__ __launch_bounds__(256) void point_tracks_kernel(PointCullArgs a) {
             mat3_vec(a.pose, P, Pc);
             const double x = Pc[0] + a.pose[9], y = Pc[1] + a.pose[10], z = Pc[2] + a.pose[11];
             if (a.success[i] != 0 && z > 0) {
-                const double r0 = a.uv_after[2 * (size_t)i] - (a.K[0] * x / z + a.K[2]);
-                const double r1 = a.uv_after[2 * (size_t)i + 1] - (a.K[1] * y / z + a.K[3]);
+                double u, v;
+                pixel_mul_first(a.K, x, y, z, u, v);
+                const double r0 = a.uv_after[2 * (size_t)i] - u;
+                const double r1 = a.uv_after[2 * (size_t)i + 1] - v;
                 const double e2 = r0 * r0 + r1 * r1;
                 good = e2 <= a.reproj * a.reproj;
             }
@@ -84,18 +83,12 @@ __global__ __launch_bounds__(256) void point_tracks_kernel(PointCullArgs a) {
 
 __global__ __launch_bounds__(1024) void point_cull_kernel(PointCullArgs a) {
     __shared__ int s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     // the candidates
     int cand = 0;
     for (int i0 = 0; i0 < a.n; i0 += 1024) {
         const int i = i0 + tid;
-        const bool c = i < a.n && a.tracks[i].w >= a.max_fail_run;
-        const unsigned long long b = __ballot(c);
-        if (lane == 0) s_w[wave] = __popcll(b);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) cand += s_w[k];
-        __syncthreads();
+        cand += block_rank<16>(i < a.n && a.tracks[i].w >= a.max_fail_run, s_w).total;
     }
     const int surv = a.n - cand;
     const bool abandoned = cand > 0 && surv < a.min_points;
@@ -110,26 +103,16 @@ __global__ __launch_bounds__(1024) void point_cull_kernel(PointCullArgs a) {
             f = abandoned || r.w < a.max_fail_run;
             a.keep[i] = f ? 1 : 0;
         }
-        const unsigned long long b = __ballot(f);
-        if (lane == 0) s_w[wave] = __popcll(b);
-        __syncthreads();
-        int wb = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = s_w[k];
-            wb += k < wave ? t : 0;
-            tot += t;
-        }
-        __syncthreads();
+        const BlockRank k = block_rank<16>(f, s_w);
         if (f) {
-            const size_t j = (size_t)(base + wb + popc_below(b, lane));
+            const size_t j = (size_t)(base + k.rank);
             a.out_pts[3 * j] = a.pts[3 * (size_t)i];
             a.out_pts[3 * j + 1] = a.pts[3 * (size_t)i + 1];
             a.out_pts[3 * j + 2] = a.pts[3 * (size_t)i + 2];
             a.out_host[j] = a.host[i];
             a.out_tracks[j] = r;
         }
-        base += tot;
+        base += k.total;
     }
     if (tid == 0) {
         a.ccounts[0] = cand;
@@ -202,10 +185,7 @@ int viso_ctx::update_tracks(int cur) {
     const size_t o = (size_t)(lk_last_rows - 1) * kMaxMapPoints;  // cur's row: the batch's last
     PointCullArgs a{};
     point_cull_scratch_at(a, cull_buf.ptr, kMaxMapPoints);
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.pts = (const double*)map_pts.ptr;
     a.n = n_map;
     a.pair_kf = (const int32_t*)lk_pair.ptr + o;
@@ -226,15 +206,13 @@ int viso_ctx::update_tracks(int cur) {
 // ahead of its insertion check).  One host sync for the counts and the
 // survivors' hosts (n_map and point_host are host state).  A cull that
 // removed something rewrites map_pts and the records in place and rebuilds
-// the LK templates, so the context stream is first ordered behind every
-// reader on lk_stream, as a retirement (mapwin.hip).
+// the LK templates: a map rewrite (begin_map_rewrite, mapwin.hip).
 int viso_ctx::cull_points() {
     const int n = n_map;
     if (n <= 0) return VISO_OK;
     if ((int)point_host.size() != n) return VISO_ERR_STATE;
     if (int rc = point_host_dev.ensure(4 * (size_t)kMaxMapPoints)) return rc;
-    if (int rc = order_after_lk(lk_seq - 1, stream)) return rc;
-    if (bg_done) VISO_HIP_CHECK(hipStreamWaitEvent(stream, bg_done, 0));
+    if (int rc = begin_map_rewrite(true)) return rc;
     PointCullArgs a{};
     point_cull_scratch_at(a, cull_buf.ptr, kMaxMapPoints);
     a.pts = (const double*)map_pts.ptr;
@@ -243,8 +221,6 @@ int viso_ctx::cull_points() {
     a.host = (const int*)point_host_dev.ptr;
     a.max_fail_run = cull_max_fail;
     a.min_points = cull_min_points;
-    VISO_HIP_CHECK(hipMemcpyAsync(point_host_dev.ptr, point_host.data(), 4 * (size_t)n, hipMemcpyHostToDevice,
-                                  stream));
     {
         TimedRegion t(timing, VISO_KERNEL_CULL, stream);
         launch_point_cull(a, stream);
@@ -260,13 +236,7 @@ int viso_ctx::cull_points() {
         return VISO_OK;
     }
     if (cand <= 0 || kept == n) return VISO_OK;
-    if (kept > 0) {
-        VISO_HIP_CHECK(hipMemcpyAsync(map_pts.ptr, a.out_pts, 24 * (size_t)kept, hipMemcpyDeviceToDevice, stream));
-        VISO_HIP_CHECK(hipMemcpyAsync(pt_tracks.ptr, a.out_tracks, 16 * (size_t)kept, hipMemcpyDeviceToDevice,
-                                      stream));
-    }
-    point_host.assign(hosts.begin(), hosts.begin() + kept);
-    n_map = kept;
+    if (int rc = end_map_rewrite(a.out_pts, a.out_tracks, hosts, kept)) return rc;
     cull_applied += 1;
     cull_removed += n - kept;
     cull_last[0] = frames;
@@ -350,10 +320,7 @@ int viso_point_tracks_update(viso_ctx* c, const double* points, const int32_t* p
         VISO_HIP_CHECK(hipMemcpyAsync(base + o_t, tracks4, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
     PointCullArgs a{};
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.pts = (const double*)(base + o_p);
     a.n = n;
     a.pair_kf = (const int32_t*)(base + o_pk);

@@ -297,10 +297,7 @@ int viso_ctx::refine_points() {
     PrefineBuf r{};
     prefine_buf_at(r, prefine_buf.ptr, prefine_window);
     PointRefineArgs a{};
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.pts = (double*)map_pts.ptr;
     a.n = n;
     a.anchor_kf = (const int32_t*)lk_tmpl_kf.ptr;
@@ -482,10 +479,7 @@ int viso_points_refine(viso_ctx* c, const double* points, const int32_t* anchor_
         VISO_HIP_CHECK(hipMemcpyAsync(base + o_uv, obs_uv, 16 * w * (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
     PointRefineArgs a{};
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.pts = (double*)(base + o_p);
     a.n = n;
     a.anchor_kf = (const int32_t*)(base + o_a);

@@ -352,10 +352,7 @@ int viso_ctx::refine_frame(int cur) {
     if (n_map <= 0 || lk_last_rows < 1 || lk_last_pts != n_map) return VISO_ERR_STATE;
     const size_t o = (size_t)(lk_last_rows - 1) * kMaxMapPoints;  // cur's row: the batch's last
     RefineArgs a{};
-    a.K[0] = p.fx;
-    a.K[1] = p.fy;
-    a.K[2] = p.cx;
-    a.K[3] = p.cy;
+    intrinsics(a.K);
     a.pts = (const double*)map_pts.ptr;
     a.pair_kf = (const int32_t*)lk_pair.ptr + o;
     a.success = (const uint8_t*)lk_succ.ptr + o;
@@ -437,10 +434,7 @@ int viso_refine_pose(viso_ctx* c, const double* points, const int32_t* pair_kf, 
         VISO_HIP_CHECK(hipMemcpyAsync(base + o_ua, uv_after, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
     RefineArgs a{};
-    a.K[0] = c->p.fx;
-    a.K[1] = c->p.fy;
-    a.K[2] = c->p.cx;
-    a.K[3] = c->p.cy;
+    c->intrinsics(a.K);
     a.pts = (const double*)(base + o_p);
     a.pair_kf = (const int32_t*)(base + o_pk);
     a.success = (const uint8_t*)(base + o_sc);

@@ -12,6 +12,8 @@
 // the left patch is staged once in LDS (64 bytes), each lane streams its
 // right patch from L1/L2; argmin by a packed (sad << 16 | d) wave min.
 // Integer work: bit-exact.
+#include "block_rank.hpp"
+#include "device_math.hpp"
 #include "kernels.hpp"
 
 namespace viso {
@@ -143,42 +145,27 @@ __global__ __launch_bounds__(256) void stereo_points_kernel(const uint8_t* __res
     }
 }
 
-// Ordered compaction of the kept points (one workgroup of 1024 threads):
-// out[j] = pts of the j-th kept keypoint, j < cap; *count = number kept
-// (uncapped).
+// Ordered compaction of the kept points (one workgroup of 1024 threads,
+// block_rank.hpp; flag[] holds 0 or 1, stereo_points_kernel's): out[j] = pts
+// of the j-th kept keypoint, j < cap; *count = number kept (uncapped).
 __global__ __launch_bounds__(1024) void stereo_compact_kernel(const int* __restrict__ flag,
                                                               const double* __restrict__ pts, int n,
                                                               double* __restrict__ out, int cap,
                                                               int* __restrict__ count) {
     __shared__ int s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
-        const int f = i < n ? flag[i] : 0;
-        int incl = f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        int wb = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int t = s_w[k];
-            wb += k < wave ? t : 0;
-            tot += t;
-        }
-        __syncthreads();
-        const int j = base + wb + incl - f;
+        const bool f = i < n && flag[i] != 0;
+        const BlockRank r = block_rank<16>(f, s_w);
+        const int j = base + r.rank;
         if (f && j < cap) {
             out[3 * (size_t)j] = pts[3 * (size_t)i];
             out[3 * (size_t)j + 1] = pts[3 * (size_t)i + 1];
             out[3 * (size_t)j + 2] = pts[3 * (size_t)i + 2];
         }
-        base += tot;
+        base += r.total;
     }
     if (tid == 0) *count = base;
 }
@@ -189,10 +176,9 @@ __global__ __launch_bounds__(256) void points_to_world_kernel(double* __restrict
                                                               const double* __restrict__ pose) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double d0 = pts[3 * (size_t)i] - pose[9], d1 = pts[3 * (size_t)i + 1] - pose[10],
-                 d2 = pts[3 * (size_t)i + 2] - pose[11];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) pts[3 * (size_t)i + k] = (pose[k] * d0 + pose[3 + k] * d1) + pose[6 + k] * d2;
+    double* P = pts + 3 * (size_t)i;
+    const double Pc[3] = {P[0], P[1], P[2]};
+    camera_to_world(pose, Pc, P);
 }
 
 }  // namespace

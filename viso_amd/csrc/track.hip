@@ -819,24 +819,6 @@ __global__ __launch_bounds__(256, FAST ? VISO_LK_MIN_WAVES_FAST : VISO_LK_MIN_WA
 // lk_point.  fp64 in both precision modes.
 constexpr double kWarpH = 4.0;  // the affine map's finite-difference step (anchor pixels)
 
-// a camera point through pose (R row-major + t) and K as project_px does;
-// returns its depth
-__device__ inline double warp_project(const double* pose, const Intrinsics& K, const double* W, double& u,
-                                      double& v) {
-    double c[3];
-    mat3_vec(pose, W, c);
-    c[0] = c[0] + pose[9];
-    c[1] = c[1] + pose[10];
-    c[2] = c[2] + pose[11];
-    const double z = c[2];
-    const double x = c[0] / z, y = c[1] / z;
-    u = x * K.fx + K.cx;
-    v = y * K.fy + K.cy;
-    return z;
-}
-
-__device__ inline bool warp_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
-
 __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[4][2][kWinW * kWinH];
     const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -883,11 +865,11 @@ __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
             const double za = Pa[2] + kp[11];
             const bool odd = lane & 1;
             const double qu = odd ? bu : bu + kWarpH, qv = odd ? bv + kWarpH : bv;
-            const double d[3] = {(qu - K.cx) / K.fx * za - kp[9], (qv - K.cy) / K.fy * za - kp[10], za - kp[11]};
+            const double Pk[3] = {(qu - K.cx) / K.fx * za, (qv - K.cy) / K.fy * za, za};
             double Wp[3];
-            for (int j = 0; j < 3; ++j) Wp[j] = (kp[j] * d[0] + kp[3 + j] * d[1]) + kp[6 + j] * d[2];
+            camera_to_world(kp, Pk, Wp);
             double uq, vq;
-            const double zq = warp_project(cur_pose, K, Wp, uq, vq);
+            const double zq = project_px_depth(cur_pose, K, Wp, uq, vq);
             const double au = (uq - uc) / kWarpH, av = (vq - vc) / kWarpH;
             A00 = readlane_f64(au, 0);
             A10 = readlane_f64(av, 0);
@@ -896,8 +878,8 @@ __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
             const double zu = readlane_f64(zq, 0), zv = readlane_f64(zq, 1);
             const double det = A00 * A11 - A01 * A10;
             double D = fabs(det);
-            const bool ok = za > 0 && zu > 0 && zv > 0 && warp_finite(A00) && warp_finite(A01) &&
-                            warp_finite(A10) && warp_finite(A11) && 1.0 / a.warp_ratio <= D && D <= a.warp_ratio;
+            const bool ok = za > 0 && zu > 0 && zv > 0 && finite_f64(A00) && finite_f64(A01) &&
+                            finite_f64(A10) && finite_f64(A11) && 1.0 / a.warp_ratio <= D && D <= a.warp_ratio;
             status = 2;
             if (__builtin_amdgcn_readfirstlane(ok ? 1 : 0)) {
                 // the inverse's four divisions on lanes 0..3
