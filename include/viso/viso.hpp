@@ -485,6 +485,40 @@ public:
         return r;
     }
 
+    // Relocalisation (viso_set_relocalise): lost_after consecutive bad
+    // tracking frames lose the context; every lost frame then aligns the
+    // keyframes to itself until one alignment is accepted.  lost_after 0 = off.
+    void SetRelocalise(int lost_after, double max_cost = 57600.0, int min_good_permille = 500, int lk_permille = 0,
+                       int iterations = 10, int max_points = 512) {
+        check(viso_set_relocalise(ctx_, lost_after, max_cost, min_good_permille, lk_permille, iterations, max_points),
+              "viso_set_relocalise");
+    }
+    // viso_get_relocalise's info[8]
+    std::array<int64_t, 8> GetRelocalise() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_relocalise(ctx_, info.data()), "viso_get_relocalise");
+        return info;
+    }
+    // the last attempt's candidate rows: poses (12 per candidate), report (20)
+    struct RelocaliseReport {
+        std::vector<double> poses, report;
+    };
+    RelocaliseReport GetRelocaliseReport() const {
+        size_t n = 0;
+        check(viso_get_relocalise_report(ctx_, nullptr, nullptr, 0, &n), "viso_get_relocalise_report");
+        RelocaliseReport r{std::vector<double>(12 * n), std::vector<double>(20 * n)};
+        if (n) check(viso_get_relocalise_report(ctx_, r.poses.data(), r.report.data(), n, &n), "viso_get_relocalise_report");
+        return r;
+    }
+    // one byte per pose: 0 tracked, 1 bad verdict, 2 lost, 3 recovered
+    std::vector<uint8_t> GetFrameStatus() const {
+        size_t n = 0;
+        check(viso_get_frame_status(ctx_, nullptr, 0, &n), "viso_get_frame_status");
+        std::vector<uint8_t> st(n);
+        if (n) check(viso_get_frame_status(ctx_, st.data(), n, &n), "viso_get_frame_status");
+        return st;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

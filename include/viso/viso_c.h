@@ -189,7 +189,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_POINTS 12 /* the record and refine launches (viso_set_point_refine) */
 #define VISO_KERNEL_LKWARP 13 /* a batched launch of the warped LK alignment (viso_set_lk_warp) */
 #define VISO_KERNEL_SEEDS 14 /* the depth seeds' creation, update and promotion launches (viso_depth_seeds_*) */
-#define VISO_KERNEL_COUNT 15
+#define VISO_KERNEL_RELOC 15 /* one relocalisation attempt: the candidates and the choice (viso_set_relocalise) */
+#define VISO_KERNEL_COUNT 16
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -676,6 +677,70 @@ int viso_depth_seeds_promote(viso_ctx* ctx, const double* kf_poses, int32_t n_kf
                              double conv_rel, int32_t max_bad, int32_t max_lost, int32_t room, int32_t* h, double* uv,
                              double* mu, double* s2, int32_t* counters, double* points, int32_t* hosts,
                              int32_t counts[4]);
+
+/* Relocalisation (the repo's own spec; no reference
+ * counterpart): a lost pose is recovered by direct alignment to the keyframes.
+ *
+ * viso_kf_align is one attempt on host data, through the launches of the frame
+ * path (VISO_KERNEL_RELOC).  kf_pyrs: n_kf (1..8) pyramids, kf_poses: n_kf x
+ * 12 (Tcw); cur_pyr: the current frame's pyramid; points: n_points x 3 world,
+ * 0 <= n_points <= 16384; the context's intrinsics.  Candidate c =
+ * (1 + n_extra) k + s (at most 16) aligns keyframe k to the current frame from
+ * k's own pose (s = 0) or from extra_seed12 (s = 1; n_extra in {0, 1},
+ * extra_seed12 NULL when 0), over the first max_points (64..1024) map points
+ * keyframe k sees (depth > 0, level-0 projection inside the image), in map
+ * order (m of them; m < 6: status 1, the pose out is the seed).  Levels 3..0,
+ * each from the result of the level above; pass j = 0..iterations (1..20) at
+ * T_j sums the direct pose's 28 terms of every good point (both 8x8 patches
+ * inside the level, depth > 0 in both cameras; n_j of them), cost_j = the
+ * squared-error sum / n_j, and then, in this order: n_j < 6 or cost_j not
+ * finite keeps T_j (exit 4, j = 0: no cost) or T_{j-1} (exit 5); cost_j >=
+ * cost_{j-1} keeps T_{j-1} (exit 1); 1 - cost_j / cost_{j-1} < 0.005 keeps T_j
+ * (exit 2); j = iterations keeps T_j (exit 0); a non-finite step H^-1 b keeps
+ * T_j (exit 3); otherwise T_{j+1} = exp(step) T_j.  Status, from level 0's
+ * result (n points, cost): 2 level 0 ended with exit 4; 3 n * 1000 <
+ * min_good_permille (1..1000) * m; 4 not (cost <= max_cost) (max_cost > 0);
+ * 0 accepted.  poses_out: n_cand x 12; report: n_cand x 20 = {status, m, n,
+ * cost, then for levels 3, 2, 1, 0: exit (-1: not run), steps applied, n,
+ * cost}, the cost NaN where there is none; *winner = the accepted candidate of
+ * the least cost (ties: the lowest index), -1 when none.  fp64 in both
+ * precision modes.  Every out-of-range or NULL argument returns VISO_ERR_ARG. */
+int viso_kf_align(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf, const uint8_t* cur_pyr,
+                  int32_t width, int32_t height, const double* points, int32_t n_points, const double* extra_seed12,
+                  int32_t n_extra, int32_t iterations, int32_t max_points, double max_cost, int32_t min_good_permille,
+                  double* poses_out, double* report, int32_t* winner);
+/* The mode in the frame path.  lost_after = 0 (default): off, nothing changes
+ * and the other arguments are not read.  On (lost_after 1..1000, lk_permille
+ * 0..1000, the rest as viso_kf_align's) frames are finished one by one, as with
+ * keyframe insertion, and every tracking frame is judged right behind its
+ * final solve and LK row (one host sync): it is bad when not (level-0 cost <=
+ * max_cost), when level-0 nGood * 1000 < min_good_permille * map points, or
+ * when lk_permille > 0 and LK successes * 1000 < lk_permille * LK pairs.  A
+ * good frame's pose becomes the last good pose.  lost_after consecutive bad
+ * frames lose the context, from the last of them on.  Every lost frame runs no
+ * direct pose and no LK alignment of its own but one attempt: all keyframes,
+ * extra seed = the last good pose.  No winner: the frame is logged with the
+ * last good pose (status 2, a NaN frame-log row).  A winner: the frame takes
+ * its pose (status 3), its LK alignment runs at that pose, the pose becomes the
+ * last good pose and tracking goes on from it.  Lost and recovered frames skip
+ * everything a tracking frame does behind its LK alignment (pose refinement,
+ * track records, observation ring, seeds, cull, insertion check) and do not
+ * count as tracking frames there.  The state stays VISO_STATE_RUNNING.  May be
+ * called while tracking (pending work is settled first). */
+int viso_set_relocalise(viso_ctx* ctx, int32_t lost_after, double max_cost, int32_t min_good_permille,
+                        int32_t lk_permille, int32_t iterations, int32_t max_points);
+/* info = {lost_after, lost now (0/1), losses in all, attempts in all,
+ * recoveries in all, then of the last attempt: frames processed before its
+ * frame (-1: none), its winner (-1: none), its candidates}. */
+int viso_get_relocalise(viso_ctx* ctx, int64_t info[8]);
+/* The last attempt's candidate rows, as viso_kf_align returns them: the first
+ * min(cap, n) are written (either output may be NULL); *n = its candidates (0
+ * before the first attempt).  VISO_ERR_STATE while the mode is off. */
+int viso_get_relocalise_report(viso_ctx* ctx, double* poses, double* report, size_t cap, size_t* n);
+/* One byte per pose index, as viso_get_poses counts them: 0 tracked, 1 tracked
+ * with a bad verdict, 2 lost (the pose is the held one), 3 recovered.  All 0
+ * with the mode off.  The first min(cap, n) are written; *n = the poses. */
+int viso_get_frame_status(viso_ctx* ctx, uint8_t* status, size_t cap, size_t* n);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

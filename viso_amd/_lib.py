@@ -19,7 +19,7 @@ ERRORS = {-1: "VISO_ERR_ARG", -2: "VISO_ERR_HIP", -3: "VISO_ERR_CAPACITY",
 STATE_INITIALIZATION, STATE_RUNNING, STATE_FINISHED = 0, 1, 2
 KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "direct": 5,
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
-              "points": 12, "lkwarp": 13, "seeds": 14}
+              "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15}
 
 
 class VisoError(RuntimeError):
@@ -121,6 +121,11 @@ SIGNATURES = {
                                 _vp, _vp, _vp],
     "viso_depth_seeds_promote": [_vp, _vp, _i32, _i32, _i32, _d, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp],
+    "viso_kf_align": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _d, _i32, _vp, _vp, _vp],
+    "viso_set_relocalise": [_vp, _i32, _d, _i32, _i32, _i32, _i32],
+    "viso_get_relocalise": [_vp, _vp],
+    "viso_get_relocalise_report": [_vp, _vp, _vp, _sz, _vp],
+    "viso_get_frame_status": [_vp, _vp, _sz, _vp],
     "viso_version": [],
     # north-star stereo VO (include/viso/viso_svo.h)
     "viso_svo_default_params": [_vp, _i32, _i32, _d, _d, _d, _d, _d],

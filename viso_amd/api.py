@@ -444,6 +444,29 @@ class Context:
                   _p(hst), len(pts), iterations, _p(rep))
         return poses, pts, rep
 
+    def kf_align(self, kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None, iterations: int = 10,
+                 max_points: int = 512, max_cost: float = 57600.0, min_good_permille: int = 500):
+        """viso_kf_align: one relocalisation attempt (viso_set_relocalise;
+        DESIGN.md §19) on host data with the context's intrinsics.  Candidate
+        (1 + n_extra) k + s aligns keyframe k to the current frame from its own
+        pose (s = 0) or from extra_seed (s = 1).  Returns dict(poses (n_cand,
+        12), report (n_cand, 20), winner)."""
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple)) else kf_pyrs,
+                                   dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        seed = None if extra_seed is None else np.ascontiguousarray(extra_seed, dtype=np.float64).reshape(12)
+        n_kf = kposes.shape[0]
+        n_cand = n_kf * (1 if seed is None else 2)
+        poses = np.zeros((n_cand, 12), np.float64)
+        report = np.zeros((n_cand, 20), np.float64)
+        winner = ctypes.c_int32(-1)
+        _lib.call("viso_kf_align", self.h, _p(kfp), _p(kposes), n_kf, _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)),
+                  width, height, _p(pts), pts.shape[0], _p(seed), 0 if seed is None else 1, int(iterations),
+                  int(max_points), float(max_cost), int(min_good_permille), _p(poses), _p(report),
+                  ctypes.byref(winner))
+        return {"poses": poses, "report": report, "winner": int(winner.value)}
+
     def timing_enable(self, on: bool = True):
         _lib.call("viso_timing_enable", self.h, 1 if on else 0)
 
@@ -480,6 +503,14 @@ def refine_pose(points, pair_kf, success, uv_before, uv_after, pose_in, iteratio
     """``Context.refine_pose`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).refine_pose(points, pair_kf, success, uv_before, uv_after,
                                                                 pose_in, iterations, huber_px, max_shift_px)
+
+
+def kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None, iterations=10, max_points=512,
+             max_cost=57600.0, min_good_permille=500, K=None, device: int = 0):
+    """``Context.kf_align`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points,
+                                                              extra_seed, iterations, max_points, max_cost,
+                                                              min_good_permille)
 
 
 def point_tracks_update(points, pair_kf, success, uv_after, pose, tracks, reproj_px=2.0, width=640, height=480,

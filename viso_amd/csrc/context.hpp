@@ -464,6 +464,41 @@ struct viso_ctx {
     int seed_candidates(viso::MonoKfArgs& a, const uint8_t* level0, const viso::PyrGeom& g, viso::FastScratch& fs,
                         const double* pose_c, const double* points, int n_points);
 
+    // relocalisation (viso_set_relocalise; reloc.hip): every
+    // tracking frame is finished inside on_new_frame and judged on its level-0
+    // nGood and cost and its LK row (one host sync); reloc_lost_after
+    // consecutive bad frames lose the context, and every lost frame makes one
+    // attempt (all keyframes, from their own poses and from the last good
+    // pose) instead of tracking.  0 = off (reloc_buf null).  reloc_buf: the
+    // last good pose (12), the verdict's LK counts (4), the last attempt's
+    // poses (16 x 12), report (16 x 20) and winner
+    int reloc_lost_after = 0, reloc_permille = 0, reloc_lk_permille = 0, reloc_iterations = 0, reloc_max_points = 0;
+    double reloc_max_cost = 0.0;
+    bool reloc_lost = false;
+    int reloc_bad_run = 0;
+    int64_t reloc_losses = 0, reloc_attempts = 0, reloc_recoveries = 0, reloc_last_frame = -1;
+    int reloc_last_winner = -1, reloc_last_cands = 0;
+    viso::DevBuf reloc_buf;
+    std::vector<uint8_t> frame_status;  // per pose index; shorter than n_poses: the rest 0
+    bool reloc_on() const { return reloc_lost_after > 0; }
+    double* reloc_good() const { return (double*)reloc_buf.ptr; }
+    double* reloc_counts() const { return (double*)reloc_buf.ptr + 12; }
+    double* reloc_poses() const { return (double*)reloc_buf.ptr + 16; }
+    double* reloc_report() const { return reloc_poses() + 12 * viso::kMaxAlignCands; }
+    int* reloc_winner() const { return (int*)(reloc_report() + viso::kAlignReport * viso::kMaxAlignCands); }
+    void set_frame_status(int log_index, uint8_t v) {
+        if (log_index < 0) return;
+        if (frame_status.size() <= (size_t)log_index) frame_status.resize((size_t)log_index + 1, 0);
+        frame_status[(size_t)log_index] = v;
+    }
+    // the verdict of the tracking frame just finished (cur's LK row is the last
+    // batch's last): *bad
+    int reloc_verdict(bool* bad);
+    // one attempt for the lost frame cur (its pose-log index li): *won
+    int reloc_attempt(int cur, int li, bool* won);
+    // a lost frame: the attempt, its status, a winner's LK alignment
+    int reloc_lost_frame(int cur, int li);
+
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;
     int64_t frames = 0;

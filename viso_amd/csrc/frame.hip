@@ -226,7 +226,7 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf};
+                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -659,7 +659,7 @@ int viso_ctx::finish_host_call() {
     // other call; with the warped alignment too (its batched launch, not the
     // host grid)
     if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || warp_on() || seeds_on() ||
-        bg_active)
+        reloc_on() || bg_active)
         return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
@@ -692,7 +692,7 @@ bool viso_ctx::host_queue_eligible() {
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
     return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-           !warp_on() && !seeds_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
+           !warp_on() && !seeds_on() && !reloc_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
@@ -815,7 +815,7 @@ int viso_ctx::stage_poses() {
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
                                       lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-                                      !warp_on() && !seeds_on() && !dpend && lk_pending.empty(); }
+                                      !warp_on() && !seeds_on() && !reloc_on() && !dpend && lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1011,6 +1011,23 @@ int viso_ctx::bg_end(bool drain, bool overlap) {
     bg_active = false;
     dpend_bg = -1;
     return VISO_OK;
+}
+
+// A lost frame's attempt and what follows it: no winner, the frame keeps the
+// last good pose (status 2); a winner, the frame takes its pose (status 3), its
+// LK alignment runs at that pose on the context stream and tracking goes on
+// from it.
+int viso_ctx::reloc_lost_frame(int cur, int li) {
+    bool won = false;
+    if (int rc = reloc_attempt(cur, li, &won)) return rc;
+    set_frame_status(li, won ? 3 : 2);
+    if (!won) return VISO_OK;
+    ++reloc_recoveries;
+    reloc_lost = false;
+    reloc_bad_run = 0;
+    hold(cur);
+    lk_pending.push_back(cur);
+    return flush_lk(stream);
 }
 
 int viso_ctx::count_lk(const std::vector<int>& row_slots, hipStream_t s) {
@@ -1391,6 +1408,22 @@ int viso_ctx::on_new_frame(int cur) {
             // fused into this frame's level 3: its pose is this frame's
             // last_frame pose)
             const bool log = n_poses < p.max_poses;
+            // relocalisation (viso_set_relocalise, reloc.hip): a lost frame
+            // runs no direct pose and no LK alignment of its own; it makes one
+            // attempt, and skips everything a tracking frame does below
+            const bool reloc = reloc_on() && n_map > 0;
+            if (reloc && reloc_lost) {
+                if (int rc = finish_call(stream)) return rc;  // (nothing is pending while the mode is on)
+                const int li = log ? n_poses : -1;
+                slots[(size_t)cur].log_index = li;
+                if (log) ++n_poses;
+                if (int rc = reloc_lost_frame(cur, li)) return rc;
+                break;
+            }
+            // a good frame's pose is the last good pose (final: the refinement's,
+            // an insertion's BA)
+            if (reloc && reloc_bad_run == 0)
+                VISO_HIP_CHECK(hipMemcpyAsync(reloc_good(), pose_of(last_slot), 96, hipMemcpyDeviceToDevice, stream));
             {
                 TimedRegion t(timing, VISO_KERNEL_DIRECT, stream);
                 DirectPrev m{};
@@ -1439,6 +1472,21 @@ int viso_ctx::on_new_frame(int cur) {
                 }
             }
             ran_tracking = true;
+            // the verdict, right behind the frame's final solve and LK row and
+            // ahead of everything that uses them (one host sync)
+            if (reloc) {
+                if (int rc = finish_call(stream)) return rc;
+                bool bad = false;
+                if (int rc = reloc_verdict(&bad)) return rc;
+                reloc_bad_run = bad ? reloc_bad_run + 1 : 0;
+                set_frame_status(dpend_log, bad ? 1 : 0);
+                if (bad && reloc_bad_run >= reloc_lost_after) {
+                    reloc_lost = true;
+                    ++reloc_losses;
+                    if (int rc = reloc_lost_frame(cur, dpend_log)) return rc;
+                    break;
+                }
+            }
             // pose refinement (viso_set_pose_refine, refine.hip): this frame's
             // final solve and its LK alignment now, then the refine launch on
             // that LK row; everything below and the next frame see its pose

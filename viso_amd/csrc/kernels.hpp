@@ -404,6 +404,43 @@ struct PointRefineArgs {
 void launch_point_obs(const PointObsArgs& a, hipStream_t stream);
 void launch_point_refine(const PointRefineArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- relocalisation
+// One attempt of the keyframe alignment (reloc.hip):
+// everything in device memory.  Candidate c = (1 + n_extra) k + s aligns
+// keyframe k to `cur` from k's own pose (s = 0) or from extra_seed (s = 1).
+constexpr int kMaxAlignCands = 16;
+constexpr int kAlignReport = 20;  // doubles per candidate
+struct KfAlignArgs {
+    double K[4];               // fx, fy, cx, cy
+    FrameDev kf[kMaxKeyframes];
+    const double* kf_poses;    // n_kf x 12
+    int n_kf;
+    FrameDev cur;
+    int w[4], h[4];            // the pyramid's level sizes
+    const double* points;      // n x 3 (world)
+    int n;
+    const double* extra_seed;  // 12 (n_extra = 1)
+    int n_extra, iterations, max_points, min_good_permille;
+    double max_cost;
+    double* poses_out;         // n_cand x 12
+    double* report;            // n_cand x kAlignReport
+    int* winner;               // 1
+    // the frame path: the winner's pose (the held pose when none wins) goes to
+    // pose_dst and, with log_index >= 0, to the pose log and its pinned mirror;
+    // a winner's pose to good_dst (the last good pose) too; the frame-log row
+    // becomes {the winner's n, its cost, NaN, NaN} (all NaN when none wins).
+    // All may be null.
+    const double* hold_pose;
+    double* pose_dst;
+    double* good_dst;
+    double* log;
+    double* log_host;
+    double* flog;
+    int log_index;
+};
+// two launches: the candidates (one workgroup each), then the choice
+void launch_kf_align(const KfAlignArgs& a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

@@ -265,6 +265,49 @@ class Viso(FrameHandler):
                       r["mu"].ctypes.data, r["s2"].ctypes.data, r["cnt"].ctypes.data, n.value, ctypes.byref(n))
         return {k: v[:n.value] for k, v in r.items()}
 
+    def set_relocalise(self, lost_after: int, max_cost: float = 57600.0, min_good_permille: int = 500,
+                       lk_permille: int = 0, iterations: int = 10, max_points: int = 512) -> None:
+        """Relocalisation (viso_set_relocalise): a tracking frame is bad when
+        its level-0 cost exceeds max_cost, its nGood falls below
+        min_good_permille of the map or (lk_permille > 0) its LK successes
+        below lk_permille of its pairs; `lost_after` consecutive bad frames
+        lose the context, and every lost frame then aligns the keyframes to
+        itself (from their own poses and from the last good pose) instead of
+        tracking, until one alignment is accepted.  0 = off."""
+        _lib.call("viso_set_relocalise", self.ctx.h, int(lost_after), float(max_cost), int(min_good_permille),
+                  int(lk_permille), int(iterations), int(max_points))
+
+    def relocalise(self) -> np.ndarray:
+        """viso_get_relocalise: int64[8] = lost_after, lost now, losses,
+        attempts and recoveries in all, then of the last attempt: frames
+        processed before its frame (-1: none), its winner (-1: none), its
+        candidates."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_relocalise", self.ctx.h, info.ctypes.data)
+        return info
+
+    def relocalise_report(self):
+        """The last attempt's candidate rows (viso_get_relocalise_report):
+        (poses (n, 12), report (n, 20))."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_relocalise_report", self.ctx.h, None, None, 0, ctypes.byref(n))
+        m = max(int(n.value), 1)
+        poses, report = np.zeros((m, 12)), np.zeros((m, 20))
+        if n.value:
+            _lib.call("viso_get_relocalise_report", self.ctx.h, poses.ctypes.data, report.ctypes.data, n.value,
+                      ctypes.byref(n))
+        return poses[:n.value], report[:n.value]
+
+    def frame_status(self) -> np.ndarray:
+        """viso_get_frame_status: one byte per pose: 0 tracked, 1 tracked with
+        a bad verdict, 2 lost (the held pose), 3 recovered."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_frame_status", self.ctx.h, None, 0, ctypes.byref(n))
+        st = np.zeros(max(int(n.value), 1), np.uint8)
+        if n.value:
+            _lib.call("viso_get_frame_status", self.ctx.h, st.ctypes.data, n.value, ctypes.byref(n))
+        return st[:n.value]
+
     def set_lk_warp(self, mode: int, max_area_ratio: float = 64.0) -> None:
         """Warped LK alignment (viso_set_lk_warp): every keyframe patch is
         warped into the current view by the affine map its point's depth and
