@@ -519,6 +519,28 @@ public:
         return st;
     }
 
+    // Rectification (viso_set_rectify): camera `cam` (0 left or mono, 1
+    // right) delivers raw frames, undistorted and rectified on the device
+    // ahead of the pyramid.  p.R takes rays of the rectified camera into the
+    // raw camera (the transpose of OpenCV's R1 / R2).  nullptr or model 0 =
+    // off.  Only before the first frame.
+    void set_rectify(int cam, const viso_rectify_params* p) { check(viso_set_rectify(ctx_, cam, p), "viso_set_rectify"); }
+    // viso_get_rectify's info[8]
+    std::array<int64_t, 8> get_rectify(int cam = 0) const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_rectify(ctx_, cam, info.data()), "viso_get_rectify");
+        return info;
+    }
+    // viso_rectify (stage entry): n raw images -> n rectified width x height
+    // images with the output intrinsics K; counts = {outside, clipped}
+    std::vector<uint8_t> Rectify(const viso_rectify_params& p, const std::array<double, 4>& K, int width, int height,
+                                 const uint8_t* raw, int n, std::array<int64_t, 2>* counts = nullptr) const {
+        std::vector<uint8_t> out((size_t)width * height * (size_t)std::max(n, 0));
+        check(viso_rectify(ctx_, &p, K.data(), width, height, raw, n, out.data(), counts ? counts->data() : nullptr),
+              "viso_rectify");
+        return out;
+    }
+
     viso_ctx* handle() const { return ctx_; }
 
 protected:

@@ -190,7 +190,10 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_LKWARP 13 /* a batched launch of the warped LK alignment (viso_set_lk_warp) */
 #define VISO_KERNEL_SEEDS 14 /* the depth seeds' creation, update and promotion launches (viso_depth_seeds_*) */
 #define VISO_KERNEL_RELOC 15 /* one relocalisation attempt: the candidates and the choice (viso_set_relocalise) */
-#define VISO_KERNEL_COUNT 16
+#define VISO_KERNEL_RECTIFY 16 /* a batched rectification launch ahead of the pyramid (viso_set_rectify) */
+#define VISO_KERNEL_PYRAMID_L1 17 /* viso_pyramid's level-1 launch alone (the stage entry only; the yardstick of
+                                    tools/bench_rectify.py) */
+#define VISO_KERNEL_COUNT 18
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -763,6 +766,77 @@ int viso_get_keyframe_poses(viso_ctx* ctx, double* Tcw12, size_t cap, size_t* n)
  * VISO_ERR_ARG on any out-of-range argument. */
 int viso_photometric_ba(viso_ctx* ctx, const uint8_t* const* kf_images, int32_t n_kf, double* kf_poses,
                         double* points, const int32_t* host, int32_t n, int32_t iterations, double* report);
+
+/* Rectification (the repo's own spec, restated in tests/rectify_ref.py;
+ * DESIGN.md §20; no reference counterpart: src/main.cpp:14-17 hard-codes the
+ * intrinsics of an ideal pinhole camera).  A per-camera lens model and
+ * rectifying rotation, applied on the device to every incoming frame ahead of
+ * the pyramid, one batched launch per ingest chunk (VISO_KERNEL_RECTIFY).
+ *
+ * The output image is width x height with the intrinsics K = (fx, fy, cx, cy)
+ * of the context (viso_params); the raw image is raw_width x raw_height with
+ * the intrinsics of this struct.  All in fp64, uncontracted, in this order,
+ * for output pixel (x, y), model VISO_RECTIFY_RADTAN:
+ *   a = (x - K.cx) / K.fx, b = (y - K.cy) / K.fy,
+ *   X = (R0 a + R1 b) + R2, Y = (R3 a + R4 b) + R5, Z = (R6 a + R7 b) + R8;
+ *   not (Z > 0): the pixel is outside;
+ *   xn = X / Z, yn = Y / Z, r2 = xn xn + yn yn, xy = xn yn,
+ *   rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *   xd = xn rad + ((2 p1) xy + p2 (r2 + 2 (xn xn))),
+ *   yd = yn rad + (p1 (r2 + 2 (yn yn)) + (2 p2) xy),
+ *   u = fx xd + cx, v = fy yd + cy.
+ * R (row-major) takes rays of the rectified camera into the raw camera: it is
+ * the transpose of the R1 / R2 that OpenCV's stereoRectify returns (identity
+ * for a single camera).  It is not checked for orthonormality.
+ * Model VISO_RECTIFY_TABLE: (u, v) = the two floats of map[y][x], widened to
+ * fp64 (any lens; viso_amd.rectify has numpy helpers that make such maps).
+ * Sampling, both models: the pixel is outside unless u > -1, u < raw_width,
+ * v > -1 and v < raw_height (a NaN is outside), and then out = fill.  Else
+ *   qu = floor(32 u + 0.5), x0 = qu >> 5, ax = qu & 31 (v likewise: y0, ay),
+ *   T.. = the raw byte at the tap, or fill where the tap is outside the raw image,
+ *   out = (T00 (32-ax)(32-ay) + T01 ax (32-ay) + T10 (32-ax) ay + T11 ax ay + 512) >> 10.
+ * Two counts per camera, made on the device when the mode is set: outside =
+ * the outside pixels; clipped = those plus the pixels with a tap of non-zero
+ * weight outside the raw image (the black border the chosen K leaves). */
+#define VISO_RECTIFY_OFF 0
+#define VISO_RECTIFY_RADTAN 1
+#define VISO_RECTIFY_TABLE 2
+typedef struct viso_rectify_params {
+    int32_t model;                 /* VISO_RECTIFY_* */
+    int32_t raw_width, raw_height; /* same limits as viso_params width / height */
+    int32_t fill;                  /* 0..255 */
+    double fx, fy, cx, cy;         /* raw intrinsics (RADTAN) */
+    double k1, k2, p1, p2, k3;     /* radial-tangential coefficients, OpenCV's order */
+    double R[9];
+    const float* map;              /* TABLE: [height][width][2] (u, v), copied */
+    int32_t reserved[4];
+} viso_rectify_params;
+/* Switches camera `cam` (0: the left or only camera, 1: the right one) on, or
+ * off (p NULL or model 0; the default: nothing changes, no launch, buffer or
+ * wait is added).  With camera 0 on viso_process_frame and viso_process_stereo
+ * expect frames of the raw size and viso_process_frames_device a frame_stride
+ * of at least raw_width x raw_height; the rectified image is level 0 of the
+ * frame's own pyramid slot.  A right image is rectified by camera 1's
+ * parameters; with camera 1 off it passes through.  viso_process_stereo has
+ * one dims for both images, so there the left and right inputs must have one
+ * size: two cameras that are both on need the same raw size, and with camera 0
+ * on and camera 1 off the raw size must equal the output size (otherwise the
+ * call returns VISO_ERR_ARG; rectify such a right image to the output size
+ * with camera 1 on, or use viso_rectify).  viso_process_frames_device likewise
+ * has one frame_stride, at least the larger of the two inputs.  VISO_ERR_ARG on a bad cam,
+ * model, size or fill, on a non-finite number, on fx or fy <= 0 (RADTAN) and
+ * on a NULL map (TABLE); VISO_ERR_STATE once the context has taken a frame. */
+int viso_set_rectify(viso_ctx* ctx, int32_t cam, const viso_rectify_params* p);
+/* info = {model, raw width, raw height, fill, outside, clipped, rectify
+ * launches that held an image of this camera, images rectified}. */
+int viso_get_rectify(viso_ctx* ctx, int32_t cam, int64_t info[8]);
+/* Stage entry (parity tests; the rig and SVO contexts' way in): n raw images
+ * (host, raw_width x raw_height each, packed) -> n rectified width x height
+ * images (host) with the output intrinsics K = {fx, fy, cx, cy}, by the launch
+ * of the frame path; counts (may be NULL) = {outside, clipped} of one image.
+ * 1 <= sizes <= 4096, n >= 1; otherwise viso_set_rectify's argument rules. */
+int viso_rectify(viso_ctx* ctx, const viso_rectify_params* p, const double K[4], int32_t width, int32_t height,
+                 const uint8_t* raw, int32_t n, uint8_t* out, int64_t counts[2]);
 
 /* Library build/version string, "viso_amd 0.1 gfx950 (HIP) src:<hash>": the
  * hash of the sources and flags it was built from (viso_amd/build.py

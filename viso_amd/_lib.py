@@ -19,7 +19,7 @@ ERRORS = {-1: "VISO_ERR_ARG", -2: "VISO_ERR_HIP", -3: "VISO_ERR_CAPACITY",
 STATE_INITIALIZATION, STATE_RUNNING, STATE_FINISHED = 0, 1, 2
 KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "direct": 5,
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
-              "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15}
+              "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15, "rectify": 16, "pyramid_l1": 17}
 
 
 class VisoError(RuntimeError):
@@ -44,6 +44,19 @@ class viso_params(ctypes.Structure):
         ("precision", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6),
     ]
 
+
+class viso_rectify_params(ctypes.Structure):
+    _fields_ = [
+        ("model", ctypes.c_int32), ("raw_width", ctypes.c_int32), ("raw_height", ctypes.c_int32),
+        ("fill", ctypes.c_int32),
+        ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+        ("k1", ctypes.c_double), ("k2", ctypes.c_double), ("p1", ctypes.c_double), ("p2", ctypes.c_double),
+        ("k3", ctypes.c_double), ("R", ctypes.c_double * 9), ("map", ctypes.c_void_p),
+        ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+RECTIFY_OFF, RECTIFY_RADTAN, RECTIFY_TABLE = 0, 1, 2
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -126,6 +139,9 @@ SIGNATURES = {
     "viso_get_relocalise": [_vp, _vp],
     "viso_get_relocalise_report": [_vp, _vp, _vp, _sz, _vp],
     "viso_get_frame_status": [_vp, _vp, _sz, _vp],
+    "viso_set_rectify": [_vp, _i32, _vp],
+    "viso_get_rectify": [_vp, _i32, _vp],
+    "viso_rectify": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],
     "viso_version": [],
     # north-star stereo VO (include/viso/viso_svo.h)
     "viso_svo_default_params": [_vp, _i32, _i32, _d, _d, _d, _d, _d],

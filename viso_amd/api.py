@@ -467,6 +467,29 @@ class Context:
                   ctypes.byref(winner))
         return {"poses": poses, "report": report, "winner": int(winner.value)}
 
+    def rectify(self, raw, K_out, size_out, counts: bool = True, **kw):
+        """viso_rectify: n raw images (n, rh, rw) or (rh, rw) -> rectified
+        (n, h, w) with the output intrinsics K_out = (fx, fy, cx, cy) and
+        size_out = (w, h), by the frame path's launch.  kw: the arguments of
+        viso_amd.rectify.params (model, fill, K_raw, dist, R, map; raw_size is
+        taken from the images).  Returns (out, (outside, clipped)) or, with
+        counts=False, out."""
+        from . import rectify as _rect
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        if raw.ndim == 2:
+            raw = raw[None]
+        n, rh, rw = raw.shape
+        w, h = int(size_out[0]), int(size_out[1])
+        p, keep = _rect.params(raw_size=(rw, rh), **kw)
+        if keep is not None and keep.shape[:2] != (h, w):
+            raise ValueError("map must be (h, w, 2) of the output size")
+        Ko = np.ascontiguousarray(K_out, dtype=np.float64).reshape(4)
+        out = np.zeros((n, h, w), np.uint8)
+        cnt = np.zeros(2, np.int64)
+        _lib.call("viso_rectify", self.h, ctypes.byref(p), _p(Ko), w, h, _p(raw), n, _p(out),
+                  _p(cnt) if counts else None)
+        return (out, (int(cnt[0]), int(cnt[1]))) if counts else out
+
     def timing_enable(self, on: bool = True):
         _lib.call("viso_timing_enable", self.h, 1 if on else 0)
 

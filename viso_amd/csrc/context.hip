@@ -212,8 +212,19 @@ int viso_pyramid(viso_ctx* c, const uint8_t* images, int32_t n, int32_t width, i
         VISO_HIP_CHECK(hipMemcpyAsync(d + g.slot * i, images + l0 * i, l0, hipMemcpyHostToDevice,
                                       c->stream));
     {
-        TimedRegion t(c->timing, VISO_KERNEL_PYRAMID, c->stream);
-        launch_pyramid(g, d, n, g.slot, c->stream);
+        // VISO_KERNEL_PYRAMID_L1: the level-1 launch alone, up to an event
+        // between it and the tail (n <= kPyrBatch: one level-1 launch)
+        hipEvent_t l1a = nullptr, l1b = nullptr;
+        if (c->timing.on(VISO_KERNEL_PYRAMID_L1) && n <= kPyrBatch) {
+            l1a = c->timing.get_event();
+            l1b = c->timing.get_event();
+            (void)hipEventRecord(l1a, c->stream);
+        }
+        {
+            TimedRegion t(c->timing, VISO_KERNEL_PYRAMID, c->stream);
+            launch_pyramid(g, d, n, g.slot, c->stream, l1b);
+        }
+        if (l1a) c->timing.pending.push_back({VISO_KERNEL_PYRAMID_L1, l1a, l1b});
     }
     VISO_HIP_CHECK(hipGetLastError());
     for (int i = 0; i < n; ++i)

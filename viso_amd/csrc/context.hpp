@@ -294,7 +294,7 @@ struct viso_ctx {
     hipEvent_t epoch_now = nullptr;  // a slot freed in the current call (rare)
     int end_epoch();
     int create_up_stream();
-    int upload_host(int s, const uint8_t* grey, int32_t w, int32_t h, int32_t stride, bool pyramid);
+    int upload_host(int s, const uint8_t* grey, int32_t w, int32_t h, int32_t stride, bool pyramid, int cam = 0);
     // PoseEstimation2d2d's E path runs on lk_stream beside the H path (no LK
     // alignment runs while initialising): fork / join events
     hipEvent_t geo_fork = nullptr, geo_join = nullptr;
@@ -499,6 +499,24 @@ struct viso_ctx {
     // a lost frame: the attempt, its status, a winner's LK alignment
     int reloc_lost_frame(int cur, int li);
 
+    // rectification (viso_set_rectify; rectify.hip): camera 0
+    // is the left (or only) camera, camera 1 the right one; model 0 = off.  A
+    // rectified frame's level 0 is written into its own slot (never
+    // borrowed).  rect_map: a TABLE camera's map; rect_raw: a camera's raw
+    // host-ingested frame (one each: the upload stream is in order);
+    // rect_right: a device chunk's rectified right images (batch_frames of
+    // them; no stage reads a right pyramid, so they have no slot).
+    // rect_info: {outside, clipped, launches, images} per camera
+    viso::RectCam rect[2];
+    viso::DevBuf rect_map[2], rect_raw[2], rect_right;
+    int64_t rect_info[2][4] = {};
+    bool rect_on(int cam) const { return rect[cam].model != 0; }
+    // the size of the frames camera `cam` is given
+    int in_w(int cam) const { return rect_on(cam) ? rect[cam].rw : p.width; }
+    int in_h(int cam) const { return rect_on(cam) ? rect[cam].rh : p.height; }
+    // one batched launch on `st`: raw src[i] of camera cam[i] -> dst[i]
+    int rectify_launch(const uint8_t* const* src, uint8_t* const* dst, const uint8_t* cam, int n, hipStream_t st);
+
     // ---------------- state (include/viso.h:44)
     int state = VISO_STATE_INITIALIZATION;
     int64_t frames = 0;
@@ -528,7 +546,9 @@ struct viso_ctx {
     int ingest_chunk(const std::vector<int>& sl, const std::vector<const uint8_t*>& l0,
                      const std::vector<const uint8_t*>& right, bool overlap_tail = false);
     // (pyramid: the frame's pyramid too, on the upload stream)
-    int ingest_host(const uint8_t* grey, int32_t w, int32_t h, int32_t stride, int* slot_out, bool pyramid = false);
+    // (cam: the camera whose frame it is — its raw size and rectification)
+    int ingest_host(const uint8_t* grey, int32_t w, int32_t h, int32_t stride, int* slot_out, bool pyramid = false,
+                    int cam = 0);
     // launch LKAlignment of every pending tracking frame (on `s`)
     int flush_lk(hipStream_t s);
     // launch the pending final solve, if any

@@ -226,7 +226,8 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf};
+                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rect_map[0],
+                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -380,13 +381,23 @@ int viso_ctx::wait_freed(int64_t fe, hipStream_t st) {
 // stream: behind the slot's last readers (its lk_stream batch: acquire_slot;
 // the context stream's: the epoch that freed it), and the context stream
 // waits for the DMA before the frame's pyramid.
-int viso_ctx::upload_host(int s, const uint8_t* grey, int32_t w, int32_t h, int32_t stride, bool pyramid) {
+int viso_ctx::upload_host(int s, const uint8_t* grey, int32_t w, int32_t h, int32_t stride, bool pyramid, int cam) {
     if (int rc = wait_freed(slots[(size_t)s].free_epoch, up_stream)) return rc;
+    // a rectified camera's frame goes to the camera's raw buffer and from
+    // there, rectified, into the slot (the upload stream is in order: the
+    // buffer's next DMA follows this launch)
+    uint8_t* const to = rect_on(cam) ? (uint8_t*)rect_raw[cam].ptr : slot_base(s);
     {
         TimedRegion t(timing, VISO_KERNEL_UPLOAD, up_stream);
         dev_tl.mark(frames, 0, up_stream);
-        VISO_HIP_CHECK(stage.upload(slot_base(s), grey, w, h, stride, up_stream, true));
+        VISO_HIP_CHECK(stage.upload(to, grey, w, h, stride, up_stream, true));
         dev_tl.mark(frames, 1, up_stream);
+    }
+    if (rect_on(cam)) {
+        const uint8_t* src = to;
+        uint8_t* dst = slot_base(s);
+        const uint8_t cm = (uint8_t)cam;
+        if (int rc = rectify_launch(&src, &dst, &cm, 1, up_stream)) return rc;
     }
     if (pyramid) {
         // the frame's pyramid behind its upload, on the same stream: both
@@ -491,8 +502,9 @@ void viso_ctx::launch_ingest_pyramid(const uint8_t* const* l0, uint8_t* const* d
     }
 }
 
-int viso_ctx::ingest_host(const uint8_t* grey, int32_t w, int32_t h, int32_t stride, int* slot_out, bool pyramid) {
-    if (w != p.width || h != p.height || stride < w || !grey) return VISO_ERR_ARG;
+int viso_ctx::ingest_host(const uint8_t* grey, int32_t w, int32_t h, int32_t stride, int* slot_out, bool pyramid,
+                          int cam) {
+    if (w != in_w(cam) || h != in_h(cam) || stride < w || !grey) return VISO_ERR_ARG;
     if (!up_stream) {
         int rc = create_up_stream();
         if (rc) return rc;
@@ -501,7 +513,7 @@ int viso_ctx::ingest_host(const uint8_t* grey, int32_t w, int32_t h, int32_t str
     if (s < 0) return VISO_ERR_CAPACITY;
     // through pinned staging (staging.hpp: a pageable hipMemcpy2DAsync
     // measured 3.25 ms per 1242x375 frame), on the upload stream
-    const int rc = upload_host(s, grey, w, h, stride, pyramid);
+    const int rc = upload_host(s, grey, w, h, stride, pyramid, cam);
     if (rc) {
         hold(s);
         drop(s);
@@ -696,7 +708,7 @@ bool viso_ctx::host_queue_eligible() {
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
-    if (w != p.width || h != p.height || stride < w || !grey) return VISO_ERR_ARG;
+    if (w != in_w(0) || h != in_h(0) || stride < w || !grey) return VISO_ERR_ARG;
     // per-frame work left by the frame-by-frame path first (in order)
     if (dpend || !lk_pending.empty()) {
         if (int rc = finish_call(lk_stream)) return rc;
@@ -715,14 +727,28 @@ int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_
         drop(s);
         return rc;
     }
+    // (a rectified camera: the DMA into its raw buffer, the rectify launch
+    // into the slot behind it, and the staging event — stage.last, which the
+    // chunk waits for — behind both)
+    const bool rect0 = rect_on(0);
+    int rc_up = VISO_OK;
     {
         TimedRegion t(timing, VISO_KERNEL_UPLOAD, up_stream);
-        const hipError_t e = stage.upload(slot_base(s), grey, w, h, stride, up_stream);
-        if (e != hipSuccess) {
-            hold(s);
-            drop(s);
-            return VISO_ERR_HIP;
-        }
+        if (stage.upload(rect0 ? (uint8_t*)rect_raw[0].ptr : slot_base(s), grey, w, h, stride, up_stream, rect0) !=
+            hipSuccess)
+            rc_up = VISO_ERR_HIP;
+    }
+    if (rect0 && !rc_up) {
+        const uint8_t* src = (const uint8_t*)rect_raw[0].ptr;
+        uint8_t* dst = slot_base(s);
+        const uint8_t cm = 0;
+        rc_up = rectify_launch(&src, &dst, &cm, 1, up_stream);
+        if (!rc_up && stage.commit(up_stream) != hipSuccess) rc_up = VISO_ERR_HIP;
+    }
+    if (rc_up) {
+        hold(s);
+        drop(s);
+        return rc_up;
     }
     hold(s);  // queued
     host_q.push_back(s);
@@ -1693,7 +1719,7 @@ int viso_process_stereo(viso_ctx* c, const uint8_t* left, const uint8_t* right,
     int sl = -1, sr = -1;
     int rc = c->ingest_host(left, dims[0], dims[1], dims[2], &sl, true);
     if (rc) return rc;
-    rc = c->ingest_host(right, dims[0], dims[1], dims[2], &sr, false);
+    rc = c->ingest_host(right, dims[0], dims[1], dims[2], &sr, false, 1);
     if (rc) {
         c->hold(sl);
         c->drop(sl);
@@ -1717,9 +1743,12 @@ int viso_process_frames_device(viso_ctx* c, const uint8_t* d_left, const uint8_t
                                int32_t n, size_t frame_stride) {
     if (!c || !d_left || n < 0) return VISO_ERR_ARG;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
-    if (frame_stride < (size_t)c->geom.w[0] * c->geom.h[0]) return VISO_ERR_ARG;
+    const bool rect_l = c->rect_on(0), rect_r = d_right && c->rect_on(1);
+    if (frame_stride < (size_t)c->in_w(0) * c->in_h(0)) return VISO_ERR_ARG;
+    if (d_right && frame_stride < (size_t)c->in_w(1) * c->in_h(1)) return VISO_ERR_ARG;
     VISO_HIP_CHECK(hipSetDevice(c->device));
     const int B = c->p.batch_frames;
+    const size_t len0 = (size_t)c->geom.w[0] * c->geom.h[0];
     for (int f0 = 0, nb = 0; f0 < n; f0 += nb) {
         RoctxRange range("viso:ingest_chunk");
         // a tracking context's chunks run LK alignment in the background,
@@ -1727,6 +1756,11 @@ int viso_process_frames_device(viso_ctx* c, const uint8_t* d_left, const uint8_t
         nb = std::min(c->bg_eligible() ? std::min(B, kLkBatch) : B, n - f0);
         std::vector<int> sl;
         std::vector<const uint8_t*> l0, right;
+        // rectified cameras: the chunk's raw images and where they go (left:
+        // the frames' own slots; right: the context's buffer)
+        std::vector<const uint8_t*> rsrc;
+        std::vector<uint8_t*> rdst;
+        std::vector<uint8_t> rcam;
         // left images only: the right image is read at level 0, in place, by
         // the stereo initialisation (no stage consumes a right pyramid)
         for (int i = 0; i < nb; ++i) {
@@ -1737,12 +1771,34 @@ int viso_process_frames_device(viso_ctx* c, const uint8_t* d_left, const uint8_t
             }
             const int f = f0 + i;
             const uint8_t* src = d_left + frame_stride * (size_t)f;
-            c->slots[(size_t)s].l0 = src;
-            c->slots[(size_t)s].borrowed = true;
+            if (rect_l) {  // (the slot's own level 0, as acquire_slot left it)
+                rsrc.push_back(src);
+                rdst.push_back(c->slot_base(s));
+                rcam.push_back(0);
+                src = c->slot_base(s);
+            } else {
+                c->slots[(size_t)s].l0 = src;
+                c->slots[(size_t)s].borrowed = true;
+            }
             c->hold(s);  // pending in this chunk
             sl.push_back(s);
             l0.push_back(src);
-            right.push_back(d_right ? d_right + frame_stride * (size_t)f : nullptr);
+            const uint8_t* rsrc_r = d_right ? d_right + frame_stride * (size_t)f : nullptr;
+            if (rect_r) {
+                uint8_t* to = (uint8_t*)c->rect_right.ptr + len0 * (size_t)i;
+                rsrc.push_back(rsrc_r);
+                rdst.push_back(to);
+                rcam.push_back(1);
+                rsrc_r = to;
+            }
+            right.push_back(rsrc_r);
+        }
+        // one batched rectify launch ahead of the chunk's pyramid
+        if (!rsrc.empty()) {
+            if (int rc = c->rectify_launch(rsrc.data(), rdst.data(), rcam.data(), (int)rsrc.size(), c->stream)) {
+                for (int x : sl) c->drop(x);
+                return rc;
+            }
         }
         if (int rc = c->ingest_chunk(sl, l0, right, f0 + nb < n && c->tail_overlap_on())) return rc;
     }

@@ -1127,6 +1127,7 @@ void launch_pyramid_frames(const PyrGeom& g, const uint8_t* const* l0, uint8_t* 
         const int oi = own && own->img >= b0 && own->img < b0 + nb ? own->img - b0 : -1;
         bool copy = oi >= 0 && l0[b0 + oi] != slot[b0 + oi];
         launch_pyr_level(g, 1, l0 + b0, slot + b0, nb, stream, own && n == 1 ? own->fast : nullptr);
+        if (own && own->l1_done) (void)hipEventRecord(own->l1_done, stream);
         PyrTailArgs ta;
         size_t lds = 0;
         if (pf_plan(g, nb, ta, lds)) {
@@ -1163,14 +1164,16 @@ void launch_pyramid_frames(const PyrGeom& g, const uint8_t* const* l0, uint8_t* 
 }
 
 void launch_pyramid(const PyrGeom& g, uint8_t* base, int n_images, size_t img_stride,
-                    hipStream_t stream) {
+                    hipStream_t stream, hipEvent_t l1_done) {
     std::vector<const uint8_t*> l0((size_t)n_images);
     std::vector<uint8_t*> slot((size_t)n_images);
     for (int i = 0; i < n_images; ++i) {
         slot[(size_t)i] = base + img_stride * (size_t)i;
         l0[(size_t)i] = slot[(size_t)i];
     }
-    launch_pyramid_frames(g, l0.data(), slot.data(), n_images, stream);
+    PyrOwn own{-1, nullptr, false};
+    own.l1_done = l1_done;
+    launch_pyramid_frames(g, l0.data(), slot.data(), n_images, stream, l1_done ? &own : nullptr);
 }
 
 

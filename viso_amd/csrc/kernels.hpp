@@ -10,7 +10,7 @@ namespace viso {
 // Builds levels 1..3 of n_images pyramids; image i's level-0 bytes live at
 // base + i*img_stride (levels follow, PyrGeom offsets).
 void launch_pyramid(const PyrGeom& g, uint8_t* base, int n_images, size_t img_stride,
-                    hipStream_t stream);
+                    hipStream_t stream, hipEvent_t l1_done = nullptr);
 // Batched pyramid over frames whose level 0 is at l0[i] and whose levels
 // 1..3 go to slot[i] + g.off[l] (n <= kPyrBatch per launch; more are split).
 constexpr int kPyrBatch = 128;
@@ -49,6 +49,7 @@ struct PyrOwn {
     int* zero = nullptr;
     int n_zero = 0;
     FastPre* fast = nullptr;
+    hipEvent_t l1_done = nullptr;  // recorded behind the level-1 launch, ahead of the tail (timing)
 };
 void launch_pyramid_frames(const PyrGeom& g, const uint8_t* const* l0, uint8_t* const* slot,
                            int n, hipStream_t stream, PyrOwn* own = nullptr);
@@ -555,5 +556,35 @@ void launch_set_pose(double* dst, const double src[12], hipStream_t stream);
 // <- *ref_pose, kf_poses[1] <- pose (one launch)
 void launch_map_create(double* cur_pose, const double pose[12], const double* pts_src, double* pts_dst, int n_pts,
                        const double* ref_pose, double* kf_poses, hipStream_t stream);
+
+// ---------------------------------------------------------------- rectification
+// viso_set_rectify (rectify.hip; the rule: viso_c.h).  One
+// camera: the lens model, the raw image's size and intrinsics, the rotation.
+struct RectCam {
+    int model = 0;  // VISO_RECTIFY_*
+    int rw = 0, rh = 0, fill = 0;
+    double Kr[4] = {};  // fx, fy, cx, cy of the raw image
+    double k[5] = {};   // k1, k2, p1, p2, k3
+    double R[9] = {};
+    const float* map = nullptr;  // TABLE: [h][w][2] (device)
+};
+constexpr int kRectBatch = 128;  // images per launch (kernel arguments stay < 4 KB)
+// n images of one launch: raw src[i] (cams[cam[i]]'s raw size) -> dst[i]
+// (w x h, output intrinsics K).
+struct RectifyArgs {
+    const uint8_t* src[kRectBatch];
+    uint8_t* dst[kRectBatch];
+    uint8_t cam[kRectBatch];
+    RectCam cams[2];
+    double K[4];
+    int w, h;
+};
+// src / dst / cam: n entries (more than kRectBatch are split; cameras of
+// different models go in a launch each).  Every camera named is on.
+void launch_rectify(const RectCam cams[2], const double K[4], int w, int h, const uint8_t* const* src,
+                    uint8_t* const* dst, const uint8_t* cam, int n, hipStream_t stream);
+// counts[0] += the outside pixels of one w x h image of `cam`, counts[1] +=
+// its clipped pixels (device ints, cleared by the caller).
+void launch_rectify_count(const RectCam& cam, const double K[4], int w, int h, int* counts, hipStream_t stream);
 
 }  // namespace viso

@@ -37,8 +37,9 @@ inline const char* phase_name(int kernel) {
     static const char* const names[] = {"viso:pyramid", "viso:fast",  "viso:klt",    "viso:ransac",
                                         "viso:select",  "viso:direct", "viso:lkalign", "viso:stereo",
                                         "viso:upload",  "viso:mapwin", "viso:refine", "viso:cull",
-                                        "viso:points",  "viso:lkwarp", "viso:seeds",  "viso:reloc"};
-    return (kernel >= 0 && kernel < 16) ? names[kernel] : "viso:phase";
+                                        "viso:points",  "viso:lkwarp", "viso:seeds",  "viso:reloc",
+                                        "viso:rectify", "viso:pyramid_l1"};
+    return (kernel >= 0 && kernel < 18) ? names[kernel] : "viso:phase";
 }
 
 }  // namespace viso

@@ -308,6 +308,31 @@ class Viso(FrameHandler):
             _lib.call("viso_get_frame_status", self.ctx.h, st.ctypes.data, n.value, ctypes.byref(n))
         return st[:n.value]
 
+    def set_rectify(self, cam: int = 0, **kw) -> None:
+        """Rectification (viso_set_rectify): camera `cam` (0 left or mono, 1
+        right) delivers raw frames of raw_size = (raw_width, raw_height), which
+        are undistorted and rectified on the device into this context's
+        pinhole image ahead of the pyramid.  kw: the arguments of
+        viso_amd.rectify.params — model (RADTAN or TABLE), raw_size, fill, K_raw
+        (the raw intrinsics), dist (k1, k2, p1, p2, k3), R (rectified -> raw
+        rays: the transpose of OpenCV's R1 / R2), map (TABLE).  No kw, or
+        model 0: off.  Only before the first frame."""
+        from . import rectify as _rect
+        if not kw or int(kw.get("model", _rect.RADTAN)) == _rect.OFF:
+            _lib.call("viso_set_rectify", self.ctx.h, int(cam), None)
+            return
+        p, keep = _rect.params(**kw)
+        if keep is not None and keep.shape[:2] != (self.height, self.width):
+            raise ValueError("map must be (height, width, 2) of this context")
+        _lib.call("viso_set_rectify", self.ctx.h, int(cam), ctypes.byref(p))  # (the map is copied)
+
+    def rectify_info(self, cam: int = 0) -> np.ndarray:
+        """viso_get_rectify: int64[8] = model, raw width, raw height, fill,
+        outside pixels, clipped pixels, rectify launches, images rectified."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_rectify", self.ctx.h, int(cam), info.ctypes.data)
+        return info
+
     def set_lk_warp(self, mode: int, max_area_ratio: float = 64.0) -> None:
         """Warped LK alignment (viso_set_lk_warp): every keyframe patch is
         warped into the current view by the affine map its point's depth and

@@ -49,8 +49,13 @@ def kitti_calib(path: str):
 class KittiSequence:
     """A KITTI odometry sequence directory (e.g. .../sequences/00)."""
 
-    def __init__(self, root: str):
+    def __init__(self, root: str, rectify=None):
+        """rectify: None (the sequence is rectified, as KITTI odometry ships),
+        or the lens parameters of its raw images — one dict of
+        viso_amd.rectify.params arguments for the left camera, or a pair
+        (left, right; either may be None) — which `configure` passes on."""
         self.root = root
+        self.rectify = tuple(rectify) if isinstance(rectify, (tuple, list)) else (rectify, None)
         self.fx, self.fy, self.cx, self.cy, self.baseline = kitti_calib(os.path.join(root, "calib.txt"))
         names = sorted(f for f in os.listdir(os.path.join(root, "image_0")) if f.endswith(".png"))
         self.n = len(names)
@@ -62,6 +67,13 @@ class KittiSequence:
 
     def __len__(self):
         return self.n
+
+    def configure(self, viso) -> None:
+        """Pass the sequence's rectification parameters on to a Viso (whose
+        width / height are the rectified size; the images here are raw)."""
+        for cam, kw in enumerate(self.rectify):
+            if kw:
+                viso.set_rectify(cam, **{"raw_size": (self.width, self.height), **kw})
 
     def image(self, frame: int, cam: int = 0) -> np.ndarray:
         return read_png(os.path.join(self.root, f"image_{cam}", f"{frame:06d}.png"))
