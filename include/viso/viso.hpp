@@ -510,6 +510,29 @@ public:
         if (n) check(viso_get_relocalise_report(ctx_, r.poses.data(), r.report.data(), n, &n), "viso_get_relocalise_report");
         return r;
     }
+    // Relocalisation seed (viso_set_reloc_seed; effective while SetRelocalise
+    // is on): a lost frame whose attempt has no winner gets a pose seed from
+    // descriptor matches and a second attempt from it.  hypotheses 0 = off.
+    void SetRelocSeed(int hypotheses = 256, int max_hamming = 48, int ratio_permille = 800, double inlier_px = 2.0,
+                      int min_inliers = 30, uint64_t seed = 0) {
+        check(viso_set_reloc_seed(ctx_, hypotheses, max_hamming, ratio_permille, inlier_px, min_inliers, seed),
+              "viso_set_reloc_seed");
+    }
+    // viso_get_reloc_seed's info[8]
+    std::array<int64_t, 8> GetRelocSeed() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_reloc_seed(ctx_, info.data()), "viso_get_reloc_seed");
+        return info;
+    }
+    // the last seed stage's report (12) and seed pose (12)
+    struct RelocSeedReport {
+        std::array<double, 12> report, pose;
+    };
+    RelocSeedReport GetRelocSeedReport() const {
+        RelocSeedReport r{};
+        check(viso_get_reloc_seed_report(ctx_, r.report.data(), r.pose.data()), "viso_get_reloc_seed_report");
+        return r;
+    }
     // one byte per pose: 0 tracked, 1 bad verdict, 2 lost, 3 recovered
     std::vector<uint8_t> GetFrameStatus() const {
         size_t n = 0;

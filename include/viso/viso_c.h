@@ -193,7 +193,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_RECTIFY 16 /* a batched rectification launch ahead of the pyramid (viso_set_rectify) */
 #define VISO_KERNEL_PYRAMID_L1 17 /* viso_pyramid's level-1 launch alone (the stage entry only; the yardstick of
                                     tools/bench_rectify.py) */
-#define VISO_KERNEL_COUNT 18
+#define VISO_KERNEL_RELOC_SEED 18 /* one relocalisation seed stage behind its FAST launches (viso_set_reloc_seed) */
+#define VISO_KERNEL_COUNT 19
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -744,6 +745,78 @@ int viso_get_relocalise_report(viso_ctx* ctx, double* poses, double* report, siz
  * with a bad verdict, 2 lost (the pose is the held one), 3 recovered.  All 0
  * with the mode off.  The first min(cap, n) are written; *n = the poses. */
 int viso_get_frame_status(viso_ctx* ctx, uint8_t* status, size_t cap, size_t* n);
+
+/* Relocalisation seed (the repo's own spec, restated in
+ * tests/reloc_seed_ref.py): a pose seed for viso_kf_align from
+ * descriptor matches, independent of where tracking stopped.
+ *
+ * viso_reloc_seed is one stage on host data, through the launches of the frame
+ * path (VISO_KERNEL_RELOC_SEED behind VISO_KERNEL_FAST).  kf_pyrs, kf_poses,
+ * cur_pyr, width, height, points, n_points: as viso_kf_align's; hosts: every
+ * point's host keyframe (0 <= hosts[i] < n_kf); start12: the start pose S.
+ *  1. Descriptor: 256 bits on pyramid level 1 at (x1, y1) = (x >> 1, y >> 1) of
+ *     a level-0 integer pixel; bit b = I1(x1 + ax, y1 + ay) < I1(x1 + bx, y1 +
+ *     by), its four offsets mix64(4 b + c) % 13 - 6 for c = 0..3 (mix64: z +=
+ *     0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >>
+ *     27) * 0x94D049BB133111EB; z ^ z >> 31); valid when 6 <= x1 < w1 - 6 and
+ *     6 <= y1 < h1 - 6; eight little-endian 32-bit words, bit b in word b / 32.
+ *  2. Point i is described in its host keyframe (that keyframe's pose and level
+ *     1) at x = (int)(u + 0.5), y = (int)(v + 0.5) of its divide-first
+ *     projection when its depth is > 0, (u, v) is inside the image and the
+ *     descriptor is valid.
+ *  3. The first max_features FAST corners of cur_pyr's level 0 (the context's
+ *     fast_thresh, the detector's order) are described on cur_pyr's level 1;
+ *     those without a valid descriptor are dropped, the order kept.
+ *  4. Every described point's best and second-best Hamming distance over the
+ *     kept corners (ties: the lowest corner index; fewer than two corners:
+ *     second = 257).  Accepted: best <= max_hamming (1..256), best * 1000 <
+ *     ratio_permille (1..1000) * second, and the corner's own best described
+ *     point is this one (ties: the lowest point index).  The match list: the
+ *     accepted points in ascending point index, M of them.
+ *  5. M < 3: status 1.  Hypothesis h (hypotheses: 1..4096) draws three distinct
+ *     list positions from r_k = mix64(seed + 4 h + k): i0 = r0 % M; i1 = r1 %
+ *     (M - 1), + 1 if >= i0; i2 = r2 % (M - 2), stepped past the smaller and
+ *     then the larger of i0, i1; ten unweighted Gauss-Newton passes from S on
+ *     their reprojection residuals (viso_refine_pose's residual and Jacobian,
+ *     sums ((m0 + m1) + m2), its solve and update); unsolved when a depth is
+ *     <= 0 or a step is not finite in any pass.  Score = the matches with depth
+ *     > 0 and squared reprojection error <= inlier_px^2 (inlier_px > 0).  Best:
+ *     the highest score, ties to the lowest h.  None solved, or the best score
+ *     < min_inliers (>= 6): status 2.
+ *  6. viso_refine_pose's rule (10 iterations, huber_px = inlier_px) from the
+ *     best hypothesis's pose on its inliers (uv_before = uv_after = the corner
+ *     pixel): the seed pose is its result when its status is 0 or 3, else the
+ *     hypothesis's pose; k* = the keyframe hosting the most inliers (ties: the
+ *     lowest index).  Status 0.
+ * report = {status, described points, kept corners, M, solved hypotheses, best
+ * h (-1: none), best score, the refinement's status (-1: not run), its cost at
+ * the result (NaN), its inliers at the result, k* (-1), 0}; pose: the seed pose
+ * (S unless the status is 0).  matches (cap x 3: point, kept corner, distance)
+ * and inliers (cap: the best hypothesis's flags) receive the first min(cap, M)
+ * rows, *n_matches = M.  Every out-of-range or NULL argument returns
+ * VISO_ERR_ARG (matches and inliers may be NULL when cap is 0). */
+int viso_reloc_seed(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf, const uint8_t* cur_pyr,
+                    int32_t width, int32_t height, const double* points, const int32_t* hosts, int32_t n_points,
+                    const double start12[12], int32_t hypotheses, int32_t max_hamming, int32_t ratio_permille,
+                    double inlier_px, int32_t min_inliers, uint64_t seed, double report[12], double pose[12],
+                    int32_t* matches, uint8_t* inliers, size_t cap, size_t* n_matches);
+/* The mode in the frame path.  hypotheses = 0 (default): off, nothing changes,
+ * nothing is launched and the other arguments are not read.  On, it takes
+ * effect only while viso_set_relocalise is on: a lost frame whose attempt has
+ * no winner runs the stage with S = the last good pose, and on status 0 a
+ * second attempt with keyframe k* alone and the seed pose as its extra seed
+ * (two candidates); its winner is handled as the first attempt's.  The second
+ * attempt counts as an attempt, and viso_get_relocalise_report returns the
+ * rows of the last attempt that ran. */
+int viso_set_reloc_seed(viso_ctx* ctx, int32_t hypotheses, int32_t max_hamming, int32_t ratio_permille,
+                        double inlier_px, int32_t min_inliers, uint64_t seed);
+/* info = {on (0/1), seed stages run, stages with status 0, recoveries through a
+ * seed, then of the last stage: M, its best score, its k*, its status (-1:
+ * none)}. */
+int viso_get_reloc_seed(viso_ctx* ctx, int64_t info[8]);
+/* The last stage's report and seed pose (NaN before the first).
+ * VISO_ERR_STATE while the mode is off. */
+int viso_get_reloc_seed_report(viso_ctx* ctx, double report[12], double pose[12]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

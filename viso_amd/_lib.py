@@ -19,7 +19,8 @@ ERRORS = {-1: "VISO_ERR_ARG", -2: "VISO_ERR_HIP", -3: "VISO_ERR_CAPACITY",
 STATE_INITIALIZATION, STATE_RUNNING, STATE_FINISHED = 0, 1, 2
 KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "direct": 5,
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
-              "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15, "rectify": 16, "pyramid_l1": 17}
+              "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15, "rectify": 16, "pyramid_l1": 17,
+              "reloc_seed": 18}
 
 
 class VisoError(RuntimeError):
@@ -139,6 +140,11 @@ SIGNATURES = {
     "viso_get_relocalise": [_vp, _vp],
     "viso_get_relocalise_report": [_vp, _vp, _vp, _sz, _vp],
     "viso_get_frame_status": [_vp, _vp, _sz, _vp],
+    "viso_set_reloc_seed": [_vp, _i32, _i32, _i32, _d, _i32, ctypes.c_uint64],
+    "viso_get_reloc_seed": [_vp, _vp],
+    "viso_get_reloc_seed_report": [_vp, _vp, _vp],
+    "viso_reloc_seed": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _d, _i32,
+                        ctypes.c_uint64, _vp, _vp, _vp, _vp, _sz, _vp],
     "viso_set_rectify": [_vp, _i32, _vp],
     "viso_get_rectify": [_vp, _i32, _vp],
     "viso_rectify": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],

@@ -467,6 +467,52 @@ class Context:
                   ctypes.byref(winner))
         return {"poses": poses, "report": report, "winner": int(winner.value)}
 
+    def set_reloc_seed(self, hypotheses: int = 256, max_hamming: int = 48, ratio_permille: int = 800,
+                       inlier_px: float = 2.0, min_inliers: int = 30, seed: int = 0) -> None:
+        """viso_set_reloc_seed; hypotheses 0 = off."""
+        _lib.call("viso_set_reloc_seed", self.h, int(hypotheses), int(max_hamming), int(ratio_permille),
+                  float(inlier_px), int(min_inliers), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def get_reloc_seed(self) -> np.ndarray:
+        """viso_get_reloc_seed: int64[8] = on, seed stages run, stages with
+        status 0, recoveries through a seed, then of the last stage: M, its
+        best score, its k*, its status."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_reloc_seed", self.h, _p(info))
+        return info
+
+    def reloc_seed_report(self):
+        """viso_get_reloc_seed_report: (report (12,), pose (12,))."""
+        report, pose = np.zeros(12), np.zeros(12)
+        _lib.call("viso_get_reloc_seed_report", self.h, _p(report), _p(pose))
+        return report, pose
+
+    def reloc_seed(self, kf_pyrs, kf_poses, cur_pyr, width, height, points, hosts, start, hypotheses: int = 256,
+                   max_hamming: int = 48, ratio_permille: int = 800, inlier_px: float = 2.0, min_inliers: int = 30,
+                   seed: int = 0):
+        """viso_reloc_seed: one seed stage on host data with the
+        context's intrinsics, FAST threshold and corner cap.  Returns
+        dict(report (12,), pose (12,), matches (M, 3) = point, kept corner,
+        distance, inliers (M,))."""
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple)) else kf_pyrs,
+                                   dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        hst = np.ascontiguousarray(hosts, dtype=np.int32).reshape(-1)
+        if hst.shape[0] != pts.shape[0]:
+            raise ValueError("hosts must have one entry per point")
+        S = np.ascontiguousarray(start, dtype=np.float64).reshape(12)
+        cap = max(pts.shape[0], 1)
+        report, pose = np.zeros(12), np.zeros(12)
+        matches, inliers = np.zeros((cap, 3), np.int32), np.zeros(cap, np.uint8)
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_reloc_seed", self.h, _p(kfp), _p(kposes), kposes.shape[0],
+                  _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)), width, height, _p(pts), _p(hst), pts.shape[0],
+                  _p(S), int(hypotheses), int(max_hamming), int(ratio_permille), float(inlier_px), int(min_inliers),
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, _p(report), _p(pose), _p(matches), _p(inliers), cap, ctypes.byref(n))
+        m = min(int(n.value), cap)
+        return {"report": report, "pose": pose, "matches": matches[:m].copy(), "inliers": inliers[:m].copy()}
+
     def rectify(self, raw, K_out, size_out, counts: bool = True, **kw):
         """viso_rectify: n raw images (n, rh, rw) or (rh, rw) -> rectified
         (n, h, w) with the output intrinsics K_out = (fx, fy, cx, cy) and

@@ -494,10 +494,32 @@ struct viso_ctx {
     // the verdict of the tracking frame just finished (cur's LK row is the last
     // batch's last): *bad
     int reloc_verdict(bool* bad);
-    // one attempt for the lost frame cur (its pose-log index li): *won
-    int reloc_attempt(int cur, int li, bool* won);
+    // one attempt for the lost frame cur (its pose-log index li): *won.
+    // only_kf < 0: every keyframe, extra seed = the last good pose; else that
+    // keyframe alone, extra seed = `seed` (device, 12)
+    int reloc_attempt(int cur, int li, bool* won, int only_kf = -1, const double* seed = nullptr);
     // a lost frame: the attempt, its status, a winner's LK alignment
     int reloc_lost_frame(int cur, int li);
+
+    // relocalisation seed (viso_set_reloc_seed; relocseed.hip):
+    // a lost frame whose attempt has no winner runs the seed stage from the
+    // last good pose (descriptor matches between the map and the frame's FAST
+    // corners, three-point hypotheses, §14's refinement); on status 0 a second
+    // attempt aligns keyframe k* alone with the seed pose as its extra seed.
+    // 0 hypotheses = off (rseed_buf null).  rseed_buf: the stage's scratch
+    // (reloc_seed_scratch_at at the map's and the corner cap's sizes), the FAST
+    // corners and their count.  rseed_last: the last stage's {M, best score,
+    // k*, status}
+    int rseed_hyp = 0, rseed_hamming = 0, rseed_ratio = 0, rseed_min_inliers = 0;
+    double rseed_px = 0.0;
+    uint64_t rseed_seed = 0;
+    int64_t rseed_runs = 0, rseed_ok = 0, rseed_recoveries = 0;
+    int64_t rseed_last[4] = {0, 0, -1, -1};
+    viso::DevBuf rseed_buf;
+    bool rseed_on() const { return rseed_hyp > 0; }
+    double* rseed_report() const;  // the report (12), then the seed pose (12)
+    // the stage for the lost frame cur: *status, *kstar (one host sync)
+    int reloc_seed_run(int cur, int* status, int* kstar);
 
     // rectification (viso_set_rectify; rectify.hip): camera 0
     // is the left (or only) camera, camera 1 the right one; model 0 = off.  A

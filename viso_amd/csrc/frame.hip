@@ -226,7 +226,7 @@ void viso_ctx::release() {
                       &geo_buf, &map_pts, &kf_poses, &direct_buf, &direct_stats,
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
-                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rect_map[0],
+                      &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rseed_buf, &rect_map[0],
                       &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1046,6 +1046,17 @@ int viso_ctx::bg_end(bool drain, bool overlap) {
 int viso_ctx::reloc_lost_frame(int cur, int li) {
     bool won = false;
     if (int rc = reloc_attempt(cur, li, &won)) return rc;
+    // the seed (viso_set_reloc_seed, relocseed.hip): no winner from the two
+    // poses at hand; a seed pose from descriptor matches, then keyframe k*
+    // alone from it
+    if (!won && rseed_on()) {
+        int status = -1, kstar = -1;
+        if (int rc = reloc_seed_run(cur, &status, &kstar)) return rc;
+        if (status == 0 && kstar >= 0) {
+            if (int rc = reloc_attempt(cur, li, &won, kstar, rseed_report() + kSeedReport)) return rc;
+            if (won) ++rseed_recoveries;
+        }
+    }
     set_frame_status(li, won ? 3 : 2);
     if (!won) return VISO_OK;
     ++reloc_recoveries;

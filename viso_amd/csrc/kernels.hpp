@@ -442,6 +442,59 @@ struct KfAlignArgs {
 // two launches: the candidates (one workgroup each), then the choice
 void launch_kf_align(const KfAlignArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------- relocalisation seed
+// One seed stage (relocseed.hip): everything in device memory.
+// The map's points are described in their host keyframes, the FAST corners of
+// `cur` in cur (256-bit BRIEF on level 1), matched both ways, and the pose is
+// solved from `start` by three-point hypotheses and §14's refinement.  The
+// scratch members are carved from reloc_seed_scratch_bytes() bytes by
+// reloc_seed_scratch_at.
+constexpr int kSeedReport = 12;   // doubles
+constexpr int kSeedMaxHyp = 4096;
+struct RelocSeedArgs {
+    double K[4];               // fx, fy, cx, cy
+    FrameDev kf[kMaxKeyframes];
+    const double* kf_poses;    // n_kf x 12
+    int n_kf;
+    FrameDev cur;
+    int w[4], h[4];            // the pyramid's level sizes
+    const double* points;      // n x 3 (world)
+    const int* host;           // n host keyframe indices
+    int n;
+    const double* start;       // 12: S
+    const int4* corners;       // FAST's {x, y, score, 0}, in the detector's order
+    const int* n_corners;      // FAST's count (uncapped)
+    int cap_corners;
+    int hypotheses, max_hamming, ratio_permille, min_inliers;
+    double inlier_px;
+    unsigned long long seed;
+    // scratch
+    int* counts;               // {described, kept corners, M, 0}; zero before the launches
+    int2* kept_xy;             // the kept corners' pixels, in order
+    uint32_t* pdesc;           // n x 8
+    uint8_t* pvalid;           // n
+    uint32_t* cdesc;           // cap_corners x 8
+    int4* pbest;               // n: {best, second, corner, 0}
+    int2* cbest;               // cap_corners: {best, point}
+    int4* matches;             // n: {point, corner, distance, inlier of the best hypothesis}
+    double* hyp_pose;          // hypotheses x 12
+    int* hyp_score;            // hypotheses: -1 unsolved (set before the launches)
+    int32_t* pair_kf;          // the inliers as an LK row over the map: n each (uv: n x 2)
+    uint8_t* success;
+    double* uv;
+    double* hyp_best;          // 12: the best hypothesis's pose (S when the status is not 0)
+    double* refine_pose;       // 12
+    double* refine_rep;        // 8
+    // results
+    double* report;            // kSeedReport
+    double* pose_out;          // 12
+};
+size_t reloc_seed_scratch_bytes(int n, int cap_corners, int hypotheses);
+size_t reloc_seed_scratch_at(RelocSeedArgs& a, void* base, int n, int cap_corners, int hypotheses);
+// behind FAST (a.corners, a.n_corners): ten launches and the refinement's
+void launch_reloc_seed(const RelocSeedArgs& a, hipStream_t stream);
+bool reloc_seed_params_ok(int hypotheses, int max_hamming, int ratio_permille, double inlier_px, int min_inliers);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

@@ -471,17 +471,20 @@ int viso_ctx::reloc_verdict(bool* bad) {
 }
 
 // One attempt for the lost frame cur: every keyframe from its own pose and
-// from the last good pose.  The choice, cur's pose (the winner's, else the
-// held one), its pose-log row and the last good pose are written on the
-// device; the host reads the winner back.
-int viso_ctx::reloc_attempt(int cur, int li, bool* won) {
+// from the last good pose (only_kf >= 0, the attempt behind a seed stage: that
+// keyframe alone, from its own pose and from `seed`).  The choice, cur's pose
+// (the winner's, else the held one), its pose-log row and the last good pose
+// are written on the device; the host reads the winner back.
+int viso_ctx::reloc_attempt(int cur, int li, bool* won, int only_kf, const double* seed) {
     *won = false;
-    const int n_kf = (int)kf_slots.size();
-    if (n_kf < 1 || n_kf > kMaxKeyframes || n_map <= 0) return VISO_ERR_STATE;
+    const int all_kf = (int)kf_slots.size();
+    if (all_kf < 1 || all_kf > kMaxKeyframes || n_map <= 0 || only_kf >= all_kf || (only_kf >= 0 && !seed))
+        return VISO_ERR_STATE;
+    const int n_kf = only_kf >= 0 ? 1 : all_kf, first = only_kf >= 0 ? only_kf : 0;
     KfAlignArgs a{};
     intrinsics(a.K);
-    for (int j = 0; j < n_kf; ++j) a.kf[j] = frame(kf_slots[(size_t)j]);
-    a.kf_poses = (const double*)kf_poses.ptr;
+    for (int j = 0; j < n_kf; ++j) a.kf[j] = frame(kf_slots[(size_t)(first + j)]);
+    a.kf_poses = (const double*)kf_poses.ptr + 12 * (size_t)first;
     a.n_kf = n_kf;
     a.cur = frame(cur);
     for (int l = 0; l < kLevels; ++l) {
@@ -490,7 +493,7 @@ int viso_ctx::reloc_attempt(int cur, int li, bool* won) {
     }
     a.points = (const double*)map_pts.ptr;
     a.n = n_map;
-    a.extra_seed = reloc_good();
+    a.extra_seed = only_kf >= 0 ? seed : reloc_good();
     a.n_extra = 1;
     a.iterations = reloc_iterations;
     a.max_points = reloc_max_points;

@@ -298,6 +298,24 @@ class Viso(FrameHandler):
                       ctypes.byref(n))
         return poses[:n.value], report[:n.value]
 
+    def set_reloc_seed(self, hypotheses: int = 256, max_hamming: int = 48, ratio_permille: int = 800,
+                       inlier_px: float = 2.0, min_inliers: int = 30, seed: int = 0) -> None:
+        """Relocalisation seed (viso_set_reloc_seed; takes effect while
+        set_relocalise is on): a lost frame whose attempt has no winner gets a
+        pose seed from descriptor matches between the map and its FAST corners,
+        and a second attempt from it.  hypotheses 0 = off."""
+        self.ctx.set_reloc_seed(hypotheses, max_hamming, ratio_permille, inlier_px, min_inliers, seed)
+
+    def reloc_seed(self) -> np.ndarray:
+        """viso_get_reloc_seed: int64[8] = on, seed stages run, stages with
+        status 0, recoveries through a seed, then of the last stage: M, its
+        best score, its k*, its status."""
+        return self.ctx.get_reloc_seed()
+
+    def reloc_seed_report(self):
+        """The last seed stage's (report (12,), pose (12,))."""
+        return self.ctx.reloc_seed_report()
+
     def frame_status(self) -> np.ndarray:
         """viso_get_frame_status: one byte per pose: 0 tracked, 1 tracked with
         a bad verdict, 2 lost (the held pose), 3 recovered."""
