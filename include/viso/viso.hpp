@@ -510,6 +510,31 @@ public:
         if (n) check(viso_get_relocalise_report(ctx_, r.poses.data(), r.report.data(), n, &n), "viso_get_relocalise_report");
         return r;
     }
+    // Brightness-compensated tracking (viso_set_brightness): every tracking
+    // frame's pose is estimated together with an affine brightness map (g, o)
+    // from the last frame to it, in place of the direct pose.  iterations 0 =
+    // off.
+    void SetBrightness(int iterations = 10) { check(viso_set_brightness(ctx_, iterations), "viso_set_brightness"); }
+    // viso_get_brightness's info[8]
+    std::array<int64_t, 8> GetBrightness() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_brightness(ctx_, info.data()), "viso_get_brightness");
+        return info;
+    }
+    // one row per pose: g, o, level-0 exit, steps over all levels
+    std::vector<double> GetBrightnessLog() const {
+        size_t n = 0;
+        check(viso_get_brightness_log(ctx_, nullptr, 0, &n), "viso_get_brightness_log");
+        std::vector<double> rows(4 * n);
+        if (n) check(viso_get_brightness_log(ctx_, rows.data(), n, &n), "viso_get_brightness_log");
+        return rows;
+    }
+    // the last frame's report, as viso_track_affine returns it
+    std::array<double, 24> GetBrightnessReport() const {
+        std::array<double, 24> r{};
+        check(viso_get_brightness_report(ctx_, r.data()), "viso_get_brightness_report");
+        return r;
+    }
     // Relocalisation seed (viso_set_reloc_seed; effective while SetRelocalise
     // is on): a lost frame whose attempt has no winner gets a pose seed from
     // descriptor matches and a second attempt from it.  hypotheses 0 = off.

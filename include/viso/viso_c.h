@@ -194,7 +194,8 @@ int viso_get_frame_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
 #define VISO_KERNEL_PYRAMID_L1 17 /* viso_pyramid's level-1 launch alone (the stage entry only; the yardstick of
                                     tools/bench_rectify.py) */
 #define VISO_KERNEL_RELOC_SEED 18 /* one relocalisation seed stage behind its FAST launches (viso_set_reloc_seed) */
-#define VISO_KERNEL_COUNT 19
+#define VISO_KERNEL_BRIGHT 19 /* one frame's brightness-compensated chain (viso_set_brightness, viso_track_affine) */
+#define VISO_KERNEL_COUNT 20
 /* (timing_get first launches what host-frame calls left pending, as the
  * getters do; an error of a frame's deferred work — its final solve or LK
  * batch — is returned by the next call on the context that launches it) */
@@ -817,6 +818,77 @@ int viso_get_reloc_seed(viso_ctx* ctx, int64_t info[8]);
 /* The last stage's report and seed pose (NaN before the first).
  * VISO_ERR_STATE while the mode is off. */
 int viso_get_reloc_seed_report(viso_ctx* ctx, double report[12], double pose[12]);
+
+/* Brightness-compensated tracking (the repo's own spec, restated in
+ * tests/bright_ref.py; no reference counterpart): the frame's
+ * pose estimated together with an affine brightness map (g, o) from the last
+ * frame to the current one, for cameras whose exposure changes.
+ *
+ * viso_track_affine is the stage on host data, through the launches of the
+ * frame path (VISO_KERNEL_BRIGHT).  last_pyr, cur_pyr: the two pyramids;
+ * points: n_points x 3 world, 0 <= n_points <= 16384; pose_last12: the last
+ * frame's pose L (Tcw); seed12: the seed pose; the context's intrinsics.  All
+ * arithmetic is fp64, uncontracted, in both precision modes.  The state is (T,
+ * g, o), (seed, 1, 0) on level 3; each lower level starts from the result of
+ * the level above.  Pass j = 0..iterations (1..20) on a level at (T_j, g_j,
+ * o_j): a point is good as in viso_kf_align (both 8x8 patches inside the level,
+ * depth > 0 under L and under T_j; n_j of them).  Per patch pixel (x outer, y
+ * inner, -4..3): R = the last level's sample at the point's pixel under L, C
+ * and (g0, g1) = the current level's sample and gradient at its pixel under
+ * T_j, e = (g_j R + o_j) - C.  A point's 14 pixel sums, each by the descending
+ * 64-leaf tree: g0 g0, g0 g1, g1 g1, e g0, e g1, e e, g0 R, g1 R, g0, g1, R R,
+ * R, e R, e.  With J0, J1 the rows of dPixeldXi at the level's scale, its 44
+ * terms: 0..27 viso_kf_align's 28 (A's upper triangle row-major, A_ab = (G0
+ * (J0a J0b) + G1 (J0a J1b + J1a J0b)) + G2 (J1a J1b); b_a = G3 J0a + G4 J1a; the
+ * cost G5), computed with this e; B_a0 = -((sum g0 R) J0a + (sum g1 R) J1a) and
+ * B_a1 = -((sum g0) J0a + (sum g1) J1a) for a = 0..5; d00 = sum R R; d01 = sum
+ * R; c0 = -(sum e R); c1 = -(sum e); d11 = 64 n_j.  Across points every term is
+ * summed by the direct pose's canonical map tree (tiles of min(64, ceil(n /
+ * 256)) consecutive points, a pairwise tree per tile and one over the tiles,
+ * +0.0 for a point that is not good); cost_j = S[27] / n_j.  The step, (g, o)
+ * eliminated: det = d00 d11 - d01 d01; q0 = (d11 c0 - d01 c1) / det; q1 = (d00
+ * c1 - d01 c0) / det; Y0[a] = (d11 B_a0 - d01 B_a1) / det; Y1[a] = (d00 B_a1 -
+ * d01 B_a0) / det; A'_ab = A_ab - (B_a0 Y0[b] + B_a1 Y1[b]) for a <= b,
+ * mirrored; b'_a = b_a - (B_a0 q0 + B_a1 q1); xi = inverse6(A') b' (viso_kf_align's
+ * solve); dg = q0 - sum_a Y0[a] xi_a, do = q1 - sum_a Y1[a] xi_a, both ascending
+ * from a = 0.  The decisions are viso_kf_align's, in its order and with its
+ * exits 0..5 and its 0.005, on (T, g, o) in place of T: exit 1 and 5 restore
+ * (T, g, o) of pass j - 1, and exit 3 is taken when any of xi, dg, do is not
+ * finite; otherwise T_{j+1} = exp(xi) T_j, g_{j+1} = g_j + dg, o_{j+1} = o_j +
+ * do.  There are no candidates, no max_points and no max_cost: pose_out12 is
+ * always the state behind level 0.  report24 = {status (0, or 2: level 0 ended
+ * with exit 4), n_points, level-0 n, level-0 cost, then for levels 3, 2, 1, 0:
+ * exit, steps applied, n, cost (NaN where there is none), then g, o, the steps
+ * applied over all levels, 0}.  Every out-of-range or NULL argument returns
+ * VISO_ERR_ARG (points may be NULL when n_points is 0). */
+int viso_track_affine(viso_ctx* ctx, const uint8_t* last_pyr, const uint8_t* cur_pyr, int32_t width, int32_t height,
+                      const double* points, int32_t n_points, const double* pose_last12, const double* seed12,
+                      int32_t iterations, double* pose_out12, double* report24);
+/* The mode in the frame path.  iterations = 0 (default): off, nothing changes,
+ * nothing is launched and nothing is allocated.  On (1..20; anything else
+ * returns VISO_ERR_ARG) every tracking frame runs this chain, seeded by the
+ * last frame's pose, instead of the direct pose, and frames are finished one by
+ * one, as with keyframe insertion.  The chain writes the frame's pose, its
+ * pose-log and frame-log rows and the level-0 n and cost (viso_get_frame_stats
+ * [9], [10]: the compensated cost) where the direct pose writes them, so
+ * everything behind the pose runs unchanged on it: LK alignment, the
+ * relocalisation verdict, refinement, records, seeds, cull, insertion.  Lost
+ * frames (viso_set_relocalise) are unchanged: viso_kf_align keeps its own
+ * arithmetic.  (g, o) is estimated afresh for every frame pair.  May be called
+ * while tracking (pending work is settled first). */
+int viso_set_brightness(viso_ctx* ctx, int32_t iterations);
+/* info = {iterations, frames tracked with the mode on, passes applied in all,
+ * frames whose level 0 ended with exit 4, then of the last such frame: its
+ * level-0 exit, its steps over all levels, its level-0 n, 0}. */
+int viso_get_brightness(viso_ctx* ctx, int64_t info[8]);
+/* One row of 4 doubles per pose index, as viso_get_poses counts them: {g, o,
+ * level-0 exit, steps over all levels}; NaN for frames tracked with the mode
+ * off and for lost frames.  The first min(cap, n) rows are written; *n = the
+ * poses.  VISO_ERR_STATE while the mode is off. */
+int viso_get_brightness_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
+/* The last frame's report, as viso_track_affine returns it (zeros before the
+ * first).  VISO_ERR_STATE while the mode is off. */
+int viso_get_brightness_report(viso_ctx* ctx, double report[24]);
 
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;

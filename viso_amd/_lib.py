@@ -21,6 +21,13 @@ KERNEL_IDS = {"pyramid": 0, "fast": 1, "klt": 2, "ransac": 3, "select": 4, "dire
               "lkalign": 6, "stereo": 7, "upload": 8, "mapwin": 9, "refine": 10, "cull": 11,
               "points": 12, "lkwarp": 13, "seeds": 14, "reloc": 15, "rectify": 16, "pyramid_l1": 17,
               "reloc_seed": 18}
+# ids whose timed region is a frame's whole chain of launches (viso_timing_get then counts chains, not launches)
+CHAIN_KERNEL_IDS = {"bright": 19}
+
+
+def kernel_id(name: str) -> int:
+    """The VISO_KERNEL_* id of a timing name."""
+    return KERNEL_IDS[name] if name in KERNEL_IDS else CHAIN_KERNEL_IDS[name]
 
 
 class VisoError(RuntimeError):
@@ -145,6 +152,11 @@ SIGNATURES = {
     "viso_get_reloc_seed_report": [_vp, _vp, _vp],
     "viso_reloc_seed": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _d, _i32,
                         ctypes.c_uint64, _vp, _vp, _vp, _vp, _sz, _vp],
+    "viso_track_affine": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
+    "viso_set_brightness": [_vp, _i32],
+    "viso_get_brightness": [_vp, _vp],
+    "viso_get_brightness_log": [_vp, _vp, _sz, _vp],
+    "viso_get_brightness_report": [_vp, _vp],
     "viso_set_rectify": [_vp, _i32, _vp],
     "viso_get_rectify": [_vp, _i32, _vp],
     "viso_rectify": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],

@@ -467,6 +467,49 @@ class Context:
                   ctypes.byref(winner))
         return {"poses": poses, "report": report, "winner": int(winner.value)}
 
+    def track_affine(self, last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations: int = 10):
+        """viso_track_affine: the brightness-compensated tracking stage
+        (viso_set_brightness) on host data with the context's
+        intrinsics: the pose of the current frame together with the affine
+        brightness map (g, o) from the last frame to it.  Returns (pose (12,),
+        report (24,))."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        L = np.ascontiguousarray(pose_last, dtype=np.float64).reshape(12)
+        S = np.ascontiguousarray(seed, dtype=np.float64).reshape(12)
+        pose, report = np.zeros(12), np.zeros(24)
+        _lib.call("viso_track_affine", self.h, _p(np.ascontiguousarray(last_pyr, dtype=np.uint8)),
+                  _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)), width, height, _p(pts), pts.shape[0], _p(L), _p(S),
+                  int(iterations), _p(pose), _p(report))
+        return pose, report
+
+    def set_brightness(self, iterations: int = 10) -> None:
+        """viso_set_brightness; iterations 0 = off."""
+        _lib.call("viso_set_brightness", self.h, int(iterations))
+
+    def get_brightness(self) -> np.ndarray:
+        """viso_get_brightness: int64[8] = iterations, frames tracked with the
+        mode on, passes applied in all, frames whose level 0 ended with exit 4,
+        then of the last frame: its level-0 exit, its steps, its level-0 n, 0."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_brightness", self.h, _p(info))
+        return info
+
+    def brightness_log(self) -> np.ndarray:
+        """viso_get_brightness_log: (poses, 4) = g, o, level-0 exit, steps over
+        all levels; NaN rows for frames tracked with the mode off."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_brightness_log", self.h, None, 0, ctypes.byref(n))
+        rows = np.zeros((max(int(n.value), 1), 4))
+        if n.value:
+            _lib.call("viso_get_brightness_log", self.h, _p(rows), n.value, ctypes.byref(n))
+        return rows[:n.value]
+
+    def brightness_report(self) -> np.ndarray:
+        """viso_get_brightness_report: the last frame's report (24,)."""
+        report = np.zeros(24)
+        _lib.call("viso_get_brightness_report", self.h, _p(report))
+        return report
+
     def set_reloc_seed(self, hypotheses: int = 256, max_hamming: int = 48, ratio_permille: int = 800,
                        inlier_px: float = 2.0, min_inliers: int = 30, seed: int = 0) -> None:
         """viso_set_reloc_seed; hypotheses 0 = off."""
@@ -541,13 +584,13 @@ class Context:
 
     def timing_select(self, kernels=None):
         """Time only the named kernels (None: all)."""
-        mask = 0xFFFFFFFF if kernels is None else sum(1 << _lib.KERNEL_IDS[k] for k in kernels)
+        mask = 0xFFFFFFFF if kernels is None else sum(1 << _lib.kernel_id(k) for k in kernels)
         _lib.call("viso_timing_select", self.h, mask)
 
     def timing(self, kernel: str):
         launches = ctypes.c_int64(0)
         ms = ctypes.c_double(0.0)
-        _lib.call("viso_timing_get", self.h, _lib.KERNEL_IDS[kernel], ctypes.byref(launches),
+        _lib.call("viso_timing_get", self.h, _lib.kernel_id(kernel), ctypes.byref(launches),
                   ctypes.byref(ms))
         return int(launches.value), float(ms.value)
 
@@ -580,6 +623,12 @@ def kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None,
     return default_context(width, height, device, K).kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points,
                                                               extra_seed, iterations, max_points, max_cost,
                                                               min_good_permille)
+
+
+def track_affine(last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations=10, K=None, device: int = 0):
+    """``Context.track_affine`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).track_affine(last_pyr, cur_pyr, width, height, points, pose_last,
+                                                                  seed, iterations)
 
 
 def point_tracks_update(points, pair_kf, success, uv_after, pose, tracks, reproj_px=2.0, width=640, height=480,

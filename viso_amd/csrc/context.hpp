@@ -521,6 +521,23 @@ struct viso_ctx {
     // the stage for the lost frame cur: *status, *kstar (one host sync)
     int reloc_seed_run(int cur, int* status, int* kstar);
 
+    // brightness-compensated tracking (viso_set_brightness; bright.hip,
+    // DESIGN.md §22): while on, every tracking frame's pose comes from the
+    // affine chain instead of the direct chain and is finished inside
+    // on_new_frame.  0 = off (bright_buf null until the mode is first set).
+    // bright_buf: the chain's scratch, the counters of viso_get_brightness
+    // (8 x int64, kept by the chain's last launch), the last report (24), the
+    // log (max_poses x 4, NaN until written)
+    int bright_iterations = 0;
+    viso::DevBuf bright_buf;
+    bool bright_on() const { return bright_iterations > 0; }
+    size_t bright_head() const { return ((viso::bright_scratch_bytes() + 255) & ~(size_t)255) + 256; }
+    long long* bright_info() const { return (long long*)((char*)bright_buf.ptr + bright_head() - 256); }
+    double* bright_report() const { return (double*)(bright_info() + 8); }
+    double* bright_log() const { return (double*)((char*)bright_buf.ptr + bright_head()); }
+    // the tracking frame cur from the frame `last` (li: its pose-log index)
+    int bright_frame(int last, int cur, int li);
+
     // rectification (viso_set_rectify; rectify.hip): camera 0
     // is the left (or only) camera, camera 1 the right one; model 0 = off.  A
     // rectified frame's level 0 is written into its own slot (never

@@ -227,7 +227,7 @@ void viso_ctx::release() {
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
                       &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rseed_buf, &rect_map[0],
-                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right};
+                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -671,7 +671,7 @@ int viso_ctx::finish_host_call() {
     // other call; with the warped alignment too (its batched launch, not the
     // host grid)
     if (state != VISO_STATE_RUNNING || kf_on() || refine_on() || cull_on() || prefine_on() || warp_on() || seeds_on() ||
-        reloc_on() || bg_active)
+        reloc_on() || bright_on() || bg_active)
         return finish_call(lk_stream);
     // the queued frames but the last have their final poses on the context
     // stream by now (each one's final solve ran in its successor's L(3))
@@ -704,7 +704,8 @@ bool viso_ctx::host_queue_eligible() {
         host_chunk = e ? std::max(0, std::min(kLkBatch, atoi(e))) : 16;
     }
     return host_chunk > 0 && state == VISO_STATE_RUNNING && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-           !warp_on() && !seeds_on() && !reloc_on() && bg_on() && direct_fits_background() && n_map > 0 && lk_tmpl.ptr;
+           !warp_on() && !seeds_on() && !reloc_on() && !bright_on() && bg_on() && direct_fits_background() && n_map > 0 &&
+           lk_tmpl.ptr;
 }
 
 int viso_ctx::queue_host_frame(const uint8_t* grey, int32_t w, int32_t h, int32_t stride) {
@@ -841,7 +842,8 @@ int viso_ctx::stage_poses() {
 // frame f's by frame f+1's merged level-3 launch, the last by the final solve.
 bool viso_ctx::bg_eligible() { return bg_on() && direct_fits_background() && state == VISO_STATE_RUNNING && n_map > 0 &&
                                       lk_tmpl.ptr && !kf_on() && !refine_on() && !cull_on() && !prefine_on() &&
-                                      !warp_on() && !seeds_on() && !reloc_on() && !dpend && lk_pending.empty(); }
+                                      !warp_on() && !seeds_on() && !reloc_on() && !bright_on() && !dpend &&
+                                      lk_pending.empty(); }
 
 // (VISO_LK_TAIL=0: every chunk's drain on the context stream, as round 5)
 bool viso_ctx::tail_overlap_on() {
@@ -1461,7 +1463,18 @@ int viso_ctx::on_new_frame(int cur) {
             // an insertion's BA)
             if (reloc && reloc_bad_run == 0)
                 VISO_HIP_CHECK(hipMemcpyAsync(reloc_good(), pose_of(last_slot), 96, hipMemcpyDeviceToDevice, stream));
-            {
+            // brightness-compensated tracking (viso_set_brightness, bright.hip):
+            // the affine chain in place of the direct chain, seeded by the last
+            // frame's pose; its last launch writes what the final solve writes,
+            // so nothing stays pending behind it
+            const bool bright = bright_on();
+            if (bright) {
+                if (int rc = finish_call(stream)) return rc;  // (nothing is pending while the mode is on)
+                dpend_log = log ? n_poses : -1;
+                if (int rc = bright_frame(last_slot, cur, dpend_log)) return rc;
+                slots[(size_t)cur].log_index = dpend_log;
+                if (log) ++n_poses;
+            } else {
                 TimedRegion t(timing, VISO_KERNEL_DIRECT, stream);
                 DirectPrev m{};
                 if (dpend) {
@@ -1482,19 +1495,21 @@ int viso_ctx::on_new_frame(int cur) {
                                      bg_active, direct_scalar_pass);
                 dev_tl.mark(frames, 4, stream);
             }
-            if (dpend) {
-                drop(dpend_cur);
-                drop(dpend_last);
+            if (!bright) {
+                if (dpend) {
+                    drop(dpend_cur);
+                    drop(dpend_last);
+                }
+                dpend = true;
+                dpend_cur = cur;
+                dpend_last = last_slot;
+                hold(cur);
+                hold(last_slot);
+                dpend_log = log ? n_poses : -1;
+                slots[(size_t)cur].log_index = dpend_log;
+                dpend_bg = bg_active ? bg_cur : -1;
+                if (log) ++n_poses;
             }
-            dpend = true;
-            dpend_cur = cur;
-            dpend_last = last_slot;
-            hold(cur);
-            hold(last_slot);
-            dpend_log = log ? n_poses : -1;
-            slots[(size_t)cur].log_index = dpend_log;
-            dpend_bg = bg_active ? bg_cur : -1;
-            if (log) ++n_poses;
             // LKAlignment (src/viso.cpp:121, 768-843): run by the chunk's
             // background kernel, or queued for the batched launch at the end
             // of this ingest call
@@ -1520,6 +1535,9 @@ int viso_ctx::on_new_frame(int cur) {
                 if (bad && reloc_bad_run >= reloc_lost_after) {
                     reloc_lost = true;
                     ++reloc_losses;
+                    // (a lost frame has no brightness row, as it has no frame-log row)
+                    if (bright && dpend_log >= 0)
+                        VISO_HIP_CHECK(hipMemsetAsync(bright_log() + 4 * (size_t)dpend_log, 0xff, 32, stream));
                     if (int rc = reloc_lost_frame(cur, dpend_log)) return rc;
                     break;
                 }

@@ -495,6 +495,43 @@ size_t reloc_seed_scratch_at(RelocSeedArgs& a, void* base, int n, int cap_corner
 void launch_reloc_seed(const RelocSeedArgs& a, hipStream_t stream);
 bool reloc_seed_params_ok(int hypotheses, int max_hamming, int ratio_permille, double inlier_px, int min_inliers);
 
+// ---------------------------------------------------------------- brightness-compensated tracking
+// One frame's chain (bright.hip): everything in device memory.
+// part / good / state are carved from bright_scratch_bytes() bytes by
+// bright_scratch_at; tile and n_tiles are set by launch_bright.
+constexpr int kBrightReport = 24;  // doubles
+constexpr int kBrightTerms = 44;   // the sums of a pass
+constexpr int kBrightState = 64;   // doubles of a state block
+struct BrightArgs {
+    double K[4];               // fx, fy, cx, cy
+    FrameDev last, cur;
+    int w[4], h[4];            // the pyramid's level sizes
+    const double* points;      // n x 3 (world)
+    int n;
+    const double* pose_last;   // 12: the last frame's pose L
+    const double* seed;        // 12
+    int iterations;
+    int tile, n_tiles;         // the canonical map tree's tiles
+    // scratch
+    double* part;              // 2 x 256 tiles x kBrightTerms
+    int* good;                 // 2 x 256
+    double* state;             // 2 x kBrightState
+    // results (the chain's last launch)
+    double* pose_out;          // 12
+    double* report;            // kBrightReport
+    double* stats;             // the direct pose's level-0 stats row ([0] n, [1] cost), or null
+    double* log;               // the pose log, its pinned host copy, the per-frame
+    double* log_host;          // log and the brightness log: row log_index of each
+    double* flog;              // (null: not written)
+    double* blog;
+    int log_index;
+    long long* info;           // viso_get_brightness's counters, or null
+};
+size_t bright_scratch_bytes();
+void bright_scratch_at(BrightArgs& a, void* base);
+int bright_launches(int iterations);  // 4 (iterations + 1) + 1
+void launch_bright(BrightArgs a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

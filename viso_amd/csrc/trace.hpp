@@ -38,8 +38,8 @@ inline const char* phase_name(int kernel) {
                                         "viso:select",  "viso:direct", "viso:lkalign", "viso:stereo",
                                         "viso:upload",  "viso:mapwin", "viso:refine", "viso:cull",
                                         "viso:points",  "viso:lkwarp", "viso:seeds",  "viso:reloc",
-                                        "viso:rectify", "viso:pyramid_l1", "viso:reloc_seed"};
-    return (kernel >= 0 && kernel < 19) ? names[kernel] : "viso:phase";
+                                        "viso:rectify", "viso:pyramid_l1", "viso:reloc_seed", "viso:bright"};
+    return (kernel >= 0 && kernel < 20) ? names[kernel] : "viso:phase";
 }
 
 }  // namespace viso

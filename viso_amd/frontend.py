@@ -316,6 +316,29 @@ class Viso(FrameHandler):
         """The last seed stage's (report (12,), pose (12,))."""
         return self.ctx.reloc_seed_report()
 
+    def set_brightness(self, iterations: int = 10) -> None:
+        """Brightness-compensated tracking (viso_set_brightness): every
+        tracking frame's pose is estimated together with an affine brightness
+        map (g, o) from the last frame to it, iterated on every pyramid level,
+        in place of the direct pose; for cameras whose exposure changes.
+        iterations 0 = off."""
+        self.ctx.set_brightness(iterations)
+
+    def brightness(self) -> np.ndarray:
+        """viso_get_brightness: int64[8] = iterations, frames tracked with the
+        mode on, passes applied in all, frames whose level 0 ended with exit 4,
+        then of the last frame: its level-0 exit, its steps, its level-0 n, 0."""
+        return self.ctx.get_brightness()
+
+    def brightness_log(self) -> np.ndarray:
+        """One row per pose: g, o, level-0 exit, steps over all levels (NaN for
+        frames tracked with the mode off and for lost frames)."""
+        return self.ctx.brightness_log()
+
+    def brightness_report(self) -> np.ndarray:
+        """The last frame's report (24,), as Context.track_affine returns it."""
+        return self.ctx.brightness_report()
+
     def frame_status(self) -> np.ndarray:
         """viso_get_frame_status: one byte per pose: 0 tracked, 1 tracked with
         a bad verdict, 2 lost (the held pose), 3 recovered."""
