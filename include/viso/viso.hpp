@@ -535,6 +535,39 @@ public:
         check(viso_get_brightness_report(ctx_, r.data()), "viso_get_brightness_report");
         return r;
     }
+    // Robust tracking (viso_set_robust): every frame the brightness chain
+    // tracks weights each patch pixel by Huber's rule with this k (grey
+    // levels).  0 = off; no effect while SetBrightness is off.
+    void SetRobust(double huber_k = 9.0) { check(viso_set_robust(ctx_, huber_k), "viso_set_robust"); }
+    // viso_get_robust's info[8]
+    std::array<int64_t, 8> GetRobust() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_robust(ctx_, info.data()), "viso_get_robust");
+        return info;
+    }
+    // the last robust frame's report, as viso_track_robust returns it
+    std::array<double, 28> GetRobustReport() const {
+        std::array<double, 28> r{};
+        check(viso_get_robust_report(ctx_, r.data()), "viso_get_robust_report");
+        return r;
+    }
+    // the last robust frame's weight mass per map point, in the map's order
+    // when that frame was tracked
+    std::vector<double> GetRobustWeights() const {
+        size_t n = 0;
+        check(viso_get_robust_weights(ctx_, nullptr, 0, &n), "viso_get_robust_weights");
+        std::vector<double> w(n);
+        if (n) check(viso_get_robust_weights(ctx_, w.data(), n, &n), "viso_get_robust_weights");
+        return w;
+    }
+    // one row per pose: mean weight, down-weighted pixels
+    std::vector<double> GetRobustLog() const {
+        size_t n = 0;
+        check(viso_get_robust_log(ctx_, nullptr, 0, &n), "viso_get_robust_log");
+        std::vector<double> rows(2 * n);
+        if (n) check(viso_get_robust_log(ctx_, rows.data(), n, &n), "viso_get_robust_log");
+        return rows;
+    }
     // Relocalisation seed (viso_set_reloc_seed; effective while SetRelocalise
     // is on): a lost frame whose attempt has no winner gets a pose seed from
     // descriptor matches and a second attempt from it.  hypotheses 0 = off.

@@ -890,6 +890,71 @@ int viso_get_brightness_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
  * first).  VISO_ERR_STATE while the mode is off. */
 int viso_get_brightness_report(viso_ctx* ctx, double report[24]);
 
+/* Robust tracking (the repo's own spec, restated in tests/robust_ref.py;
+ * DESIGN.md §23; no reference counterpart): viso_track_affine's chain with a
+ * Huber weight per patch pixel, so that an occluder, a specular patch or a map
+ * point of wrong depth no longer votes at full weight.  huber_k is in grey
+ * levels of the current image; no scale is estimated from the residuals.
+ *
+ * viso_track_robust is the stage on host data, through the launches of the
+ * frame path (VISO_KERNEL_BRIGHT).  It is viso_track_affine's rule with these
+ * changes and no others; all arithmetic is fp64 and uncontracted.  Per patch
+ * pixel, with e = (g_j R + o_j) - C: r = |e|; out = r > k (strict); w = out ? k
+ * / r : 1.0.  Each of the 14 pixel sums has the leaf w * x, x being
+ * viso_track_affine's leaf computed as there (w * (g0 * g0), w * (e * R), ...);
+ * the exception is sum 5, the cost, whose leaf is out ? k * (2.0 * r - k) : e *
+ * e (twice the Huber function).  A fifteenth sum, sum w, by the same descending
+ * 64-leaf tree, and the point's count of `out` pixels (an exact integer in a
+ * double).  A point's 46 terms: 0..43 as in viso_track_affine from the weighted
+ * sums, 44 = sum w, 45 = the count; all 46 go through the canonical map tree,
+ * +0.0 for a point that is not good.  The step takes d11 = S[44] in place of 64
+ * n_j and is otherwise unchanged; cost_j = S[27] / n_j is the Huber cost.  The
+ * decisions, the exits 0..5, the restore on exits 1 and 5, exit 3 on a
+ * non-finite value and the level hand-down are unchanged.  With a k that no
+ * residual exceeds every w is 1.0, S[44] is 64 n_j exactly and the result is
+ * viso_track_affine's bit for bit.
+ * report28 = {columns 0..22 as viso_track_affine's, k, then S[44] and S[45] of
+ * the last pass evaluated on level 0, 0, 0}.  weights (n_points doubles, or
+ * NULL): that pass's sum w per point, 0 where the point is not good.  "The last
+ * pass evaluated" is the last pass whose sums were formed: after exit 1 or 5
+ * that is the rejected pass, not the one whose state was kept.
+ * Arguments as viso_track_affine's; huber_k must be finite with 0 < k <= 1e300
+ * (anything else, NaN included, returns VISO_ERR_ARG). */
+int viso_track_robust(viso_ctx* ctx, const uint8_t* last_pyr, const uint8_t* cur_pyr, int32_t width, int32_t height,
+                      const double* points, int32_t n_points, const double* pose_last12, const double* seed12,
+                      int32_t iterations, double huber_k, double* pose_out12, double* report28, double* weights);
+/* The mode in the frame path.  huber_k = 0 (default): off.  While on (finite, 0
+ * < k <= 1e300; anything else returns VISO_ERR_ARG), every frame that the
+ * brightness chain tracks (viso_set_brightness) runs the robust form with this
+ * k; the value is kept across viso_set_brightness off and on.  With the
+ * brightness mode off it changes nothing, launches nothing and allocates
+ * nothing until that mode is on.  Everything behind the pose runs unchanged and
+ * reads the Huber level-0 cost from viso_get_frame_stats [10]; the
+ * relocalisation verdict (viso_set_relocalise's max_cost) therefore judges the
+ * Huber cost, which is at most the plain one.  The brightness log, report and
+ * counters are kept as with the mode off.  May be called while tracking
+ * (pending work is settled first). */
+int viso_set_robust(viso_ctx* ctx, double huber_k);
+/* info = {on (0/1), frames tracked robustly, then of the last such frame: its
+ * down-weighted pixels (report column 25) and its level-0 n, 0, 0, 0, 0}. */
+int viso_get_robust(viso_ctx* ctx, int64_t info[8]);
+/* The last robust frame's report, as viso_track_robust returns it (zeros before
+ * the first).  This and the two getters below return VISO_ERR_STATE until the
+ * mode and the brightness mode have been on together for the first time. */
+int viso_get_robust_report(viso_ctx* ctx, double report[28]);
+/* The last robust frame's weight mass per map point (the stage's weights): the
+ * first min(cap, n) values are written; *n = the map points that frame tracked.
+ * The order is the map's when that frame was tracked (viso_get_points then).
+ * Insertion behind the frame appends points, which have no value here; culling
+ * or a retired keyframe compacts the map, after which index i here is no longer
+ * point i of viso_get_points: read the weights before the next call that may
+ * change the map, or keep the points read at the same time. */
+int viso_get_robust_weights(viso_ctx* ctx, double* w, size_t cap, size_t* n);
+/* One row of 2 doubles per pose index, as viso_get_poses counts them: {report
+ * column 24 / (64 x level-0 n): the mean weight, report column 25}; NaN for
+ * frames not tracked robustly and for lost frames. */
+int viso_get_robust_log(viso_ctx* ctx, double* rows, size_t cap, size_t* n);
+
 /* Photometric bundle adjustment (the repo's own spec of the BA that
  * include/bundle_adjuster.h:22-106 sketches with g2o, SURVEY.md §8(f) row 4;
  * oracle/oracle_ba.cpp): after every stereo keyframe insertion, `iterations`

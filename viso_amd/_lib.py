@@ -157,6 +157,12 @@ SIGNATURES = {
     "viso_get_brightness": [_vp, _vp],
     "viso_get_brightness_log": [_vp, _vp, _sz, _vp],
     "viso_get_brightness_report": [_vp, _vp],
+    "viso_track_robust": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _d, _vp, _vp, _vp],
+    "viso_set_robust": [_vp, _d],
+    "viso_get_robust": [_vp, _vp],
+    "viso_get_robust_report": [_vp, _vp],
+    "viso_get_robust_weights": [_vp, _vp, _sz, _vp],
+    "viso_get_robust_log": [_vp, _vp, _sz, _vp],
     "viso_set_rectify": [_vp, _i32, _vp],
     "viso_get_rectify": [_vp, _i32, _vp],
     "viso_rectify": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp],

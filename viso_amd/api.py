@@ -510,6 +510,62 @@ class Context:
         _lib.call("viso_get_brightness_report", self.h, _p(report))
         return report
 
+    def track_robust(self, last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations: int = 10,
+                     huber_k: float = 9.0, weights: bool = True):
+        """viso_track_robust: track_affine's stage with a Huber weight per
+        patch pixel (viso_set_robust); huber_k in grey levels.
+        Returns (pose (12,), report (28,), weights (n,): the weight mass per
+        point of the last pass evaluated on level 0, or None with
+        weights=False)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        L = np.ascontiguousarray(pose_last, dtype=np.float64).reshape(12)
+        S = np.ascontiguousarray(seed, dtype=np.float64).reshape(12)
+        pose, report = np.zeros(12), np.zeros(28)
+        w = np.zeros(max(pts.shape[0], 1)) if weights else None
+        _lib.call("viso_track_robust", self.h, _p(np.ascontiguousarray(last_pyr, dtype=np.uint8)),
+                  _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)), width, height, _p(pts), pts.shape[0], _p(L), _p(S),
+                  int(iterations), float(huber_k), _p(pose), _p(report), _p(w))
+        return pose, report, None if w is None else w[:pts.shape[0]]
+
+    def set_robust(self, huber_k: float = 9.0) -> None:
+        """viso_set_robust: Huber weights in every frame the
+        brightness chain tracks; huber_k 0 = off."""
+        _lib.call("viso_set_robust", self.h, float(huber_k))
+
+    def get_robust(self) -> np.ndarray:
+        """viso_get_robust: int64[8] = on, frames tracked robustly, then of the
+        last such frame: its down-weighted pixels, its level-0 n, 0..."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_robust", self.h, _p(info))
+        return info
+
+    def robust_report(self) -> np.ndarray:
+        """viso_get_robust_report: the last robust frame's report (28,)."""
+        report = np.zeros(28)
+        _lib.call("viso_get_robust_report", self.h, _p(report))
+        return report
+
+    def robust_weights(self) -> np.ndarray:
+        """viso_get_robust_weights: the last robust frame's weight mass per map
+        point, in the map's order when that frame was tracked."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_robust_weights", self.h, None, 0, ctypes.byref(n))
+        w = np.zeros(max(int(n.value), 1))
+        if n.value:
+            _lib.call("viso_get_robust_weights", self.h, _p(w), n.value, ctypes.byref(n))
+        return w[:n.value]
+
+    def robust_log(self) -> np.ndarray:
+        """viso_get_robust_log: (poses, 2) = mean weight (report 24 / (64 x
+        level-0 n)), down-weighted pixels; NaN rows for frames not tracked
+        robustly."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_robust_log", self.h, None, 0, ctypes.byref(n))
+        rows = np.zeros((max(int(n.value), 1), 2))
+        if n.value:
+            _lib.call("viso_get_robust_log", self.h, _p(rows), n.value, ctypes.byref(n))
+        return rows[:n.value]
+
     def set_reloc_seed(self, hypotheses: int = 256, max_hamming: int = 48, ratio_permille: int = 800,
                        inlier_px: float = 2.0, min_inliers: int = 30, seed: int = 0) -> None:
         """viso_set_reloc_seed; hypotheses 0 = off."""
@@ -629,6 +685,13 @@ def track_affine(last_pyr, cur_pyr, width, height, points, pose_last, seed, iter
     """``Context.track_affine`` on the cached context of intrinsics K."""
     return default_context(width, height, device, K).track_affine(last_pyr, cur_pyr, width, height, points, pose_last,
                                                                   seed, iterations)
+
+
+def track_robust(last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations=10, huber_k=9.0, K=None,
+                 device: int = 0):
+    """``Context.track_robust`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).track_robust(last_pyr, cur_pyr, width, height, points, pose_last,
+                                                                  seed, iterations, huber_k)
 
 
 def point_tracks_update(points, pair_kf, success, uv_after, pose, tracks, reproj_px=2.0, width=640, height=480,

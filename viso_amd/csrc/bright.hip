@@ -21,6 +21,13 @@
 // launch writes the pose, its log rows, the level-0 stats and the report.  No
 // grid-wide barrier, no atomics, no inline assembly, no host synchronisation
 // inside the chain; fp64 in both precision modes, -ffp-contract=off.
+//
+// The robust form (viso_track_robust, viso_set_robust; DESIGN.md §23, restated
+// in tests/robust_ref.py) is the same chain with a Huber weight per patch
+// pixel: the kernel and the decision are templates on the form, the plain
+// instantiation is the code above unchanged, the robust one carries 46 terms
+// (sum w and the count of down-weighted pixels behind the 44) and writes every
+// pass's weight mass per point.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -34,7 +41,23 @@ namespace {
 
 constexpr int kBrWaves = 8;
 constexpr int kBrLanes = 64 * kBrWaves;
-constexpr int kBrTerms = kBrightTerms;     // 28 + B (12) + d00, d01, c0, c1
+// the two forms of the chain: the plain one (viso_track_affine) and the robust
+// one (viso_track_robust), which weights every patch pixel by
+// Huber's rule and carries two more terms (sum w, the down-weighted pixels)
+template <bool kRobust>
+struct BrForm;
+template <>
+struct BrForm<false> {
+    using Args = BrightArgs;
+    static constexpr int kTerms = kBrightTerms;  // 28 + B (12) + d00, d01, c0, c1
+};
+template <>
+struct BrForm<true> {
+    using Args = RobustArgs;
+    static constexpr int kTerms = kRobustTerms;  // + sum w, the count of |e| > k
+};
+__device__ inline const BrightArgs& br_base(const BrightArgs& a) { return a; }
+__device__ inline const BrightArgs& br_base(const RobustArgs& a) { return a.b; }
 constexpr int kBrMaxTiles = 256;           // map_tile's groups
 constexpr int kBrMaxTile = 64;             // points per tile at most
 constexpr double kBrDeltaThresh = 0.005;   // the reference's delta_thresh
@@ -45,9 +68,10 @@ constexpr int kStPass = 1;     // j
 constexpr int kStPending = 2;  // the previous launch left a pass's partials
 constexpr int kStT = 3;        // T (12), g, o
 constexpr int kStPrev = 17;    // pass j - 1: T (12), g, o, cost, n
-constexpr int kStReport = 33;  // the report (24)
-static_assert(kStReport + kBrightReport <= kBrightState, "state block");
+constexpr int kStReport = 33;  // the report (24; the robust form's 28)
+static_assert(kStReport + kBrightReport <= kBrightState && kStReport + kRobustReport <= kBrightState, "state block");
 
+template <int kBrTerms>
 struct BrightLds {
     double acc[kBrMaxTile][kBrTerms];  // a tile's point rows; the prologue's tile sums
     double st[kBrightState];
@@ -82,9 +106,10 @@ __device__ inline double project_level(const double* pose, const double* K, cons
 }
 
 // oracle_common.hpp tree_sum over the rows 0 .. m - 1 of L.acc (m a power of
-// two, the padding rows zero), all 44 columns at once; the sums end in row 0.
+// two, the padding rows zero), all columns at once; the sums end in row 0.
 // Called by every thread of the workgroup.
-__device__ inline void lds_tree(BrightLds& L, int m, int tid) {
+template <int kBrTerms>
+__device__ inline void lds_tree(BrightLds<kBrTerms>& L, int m, int tid) {
     for (int s = 1; s < m; s <<= 1) {
         __syncthreads();
         const int pairs = m / (2 * s);
@@ -173,8 +198,11 @@ __device__ inline void inverse6_regs(const double* Hin, double* x) {
 
 // The decisions of pass j and the step behind the pass's sums L.S / L.n: the
 // level's result (its report row, the next level from pass 0) or the next
-// state of this level.  One lane.
-__device__ void bright_decide(BrightLds& L, int iterations) {
+// state of this level.  One lane.  The robust form: d11 = S[44] (sum w) in
+// place of 64 n, and level 0's exit keeps S[44] and S[45] of the pass it judged
+// (the last pass whose sums were formed) in report columns 24 and 25.
+template <bool kRobust>
+__device__ void bright_decide(BrightLds<BrForm<kRobust>::kTerms>& L, int iterations) {
     double* st = L.st;
     const int q = (int)st[kStLevel], j = (int)st[kStPass];
     const int n = L.n;
@@ -198,7 +226,8 @@ __device__ void bright_decide(BrightLds& L, int iterations) {
     if (ex < 0) {
         // (g, o) eliminated: A' = A - B D^-1 B^T, b' = b - B D^-1 c
         const double d00 = S[40], d01 = S[41], c0 = S[42], c1 = S[43];
-        const double d11 = 64.0 * (double)n;
+        double d11 = 64.0 * (double)n;
+        if constexpr (kRobust) d11 = S[44];
         const double det = d00 * d11 - d01 * d01;
         const double q0 = (d11 * c0 - d01 * c1) / det;
         const double q1 = (d00 * c1 - d01 * c0) / det;
@@ -258,6 +287,10 @@ __device__ void bright_decide(BrightLds& L, int iterations) {
             rep[3] = r_cost;
             rep[20] = st[kStT + 12];
             rep[21] = st[kStT + 13];
+            if constexpr (kRobust) {
+                rep[24] = S[44];
+                rep[25] = S[45];
+            }
         }
         st[kStLevel] = (double)(q + 1);
         st[kStPass] = 0.0;
@@ -283,8 +316,12 @@ __device__ void bright_decide(BrightLds& L, int iterations) {
 }
 
 // Launch k of the chain (last: the launch that writes the results).
-__global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int k, int last) {
-    __shared__ BrightLds L;
+template <bool kRobust>
+__global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(typename BrForm<kRobust>::Args args, int k,
+                                                               int last) {
+    constexpr int kBrTerms = BrForm<kRobust>::kTerms;
+    const BrightArgs& a = br_base(args);
+    __shared__ BrightLds<kBrTerms> L;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int nt = a.n_tiles;
     const double* st_in = a.state + (size_t)(k & 1) * kBrightState;
@@ -302,6 +339,8 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
             if (tid >= kStT && tid < kStT + 12) v = a.seed[tid - kStT];
             if (tid == kStT + 12) v = 1.0;
             if (tid == kStReport + 1) v = (double)a.n;
+            if constexpr (kRobust)
+                if (tid == kStReport + 23) v = args.huber_k;
         } else {
             v = st_in[tid];
         }
@@ -336,7 +375,7 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
         if (tid < kBrTerms) L.S[tid] = L.acc[0][tid];
         __syncthreads();
         if (tid == 0) {
-            bright_decide(L, a.iterations);
+            bright_decide<kRobust>(L, a.iterations);
             L.st[kStPending] = 0.0;
         }
         __syncthreads();
@@ -358,7 +397,25 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
                                        __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
-        if (tid < kBrightReport) a.report[tid] = rep[tid];
+        if constexpr (kRobust) {
+            // the plain report keeps its column 23 (0); the robust one has k there
+            if (tid < kBrightReport && a.report) a.report[tid] = tid == 23 ? 0.0 : rep[tid];
+            if (tid < kRobustReport) args.report[tid] = rep[tid];
+            if (tid == 0) {
+                if (args.rlog && a.log_index >= 0) {
+                    double* row = args.rlog + 2 * (size_t)a.log_index;
+                    row[0] = rep[24] / (64.0 * rep[2]);
+                    row[1] = rep[25];
+                }
+                if (args.info) {
+                    args.info[1] = args.info[1] + 1;
+                    args.info[2] = (long long)rep[25];
+                    args.info[3] = (long long)rep[2];
+                }
+            }
+        } else {
+            if (tid < kBrightReport) a.report[tid] = rep[tid];
+        }
         if (tid == 0) {
             if (a.stats) {
                 a.stats[0] = rep[2];
@@ -422,6 +479,8 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
     }
     const double px = (double)((lane >> 3) - kHalfPatch), py = (double)((lane & 7) - kHalfPatch);
     const double hp = 4.0;
+    double hk = 0.0;  // Huber's k
+    if constexpr (kRobust) hk = args.huber_k;
     if (blockIdx.x == 0 && tid < kBrightState) st_out[tid] = tid == kStPending ? 1.0 : L.st[tid];
 
     for (int tile = blockIdx.x; tile < nt; tile += gridDim.x) {
@@ -431,6 +490,7 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
         int cnt = 0;
         for (int p = wave; p < pc; p += kBrWaves) {
             double term = 0.0;  // the padding rows, and a point that is not good
+            double mass = 0.0;  // (robust) the point's sum w
             bool good = false;
             double ur = 0, vr = 0, uc = 0, vc = 0, Pr[3], Pc[3] = {0, 0, 1};
             if (p < c) {
@@ -466,11 +526,28 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
                 double g0, g1;
                 gradient_px(cimg, w, h, xc, yc, g0, g1);
                 double G[15];
-                wave_tree_sum3_desc(g0 * g0, g0 * g1, g1 * g1, G[0], G[1], G[2]);
-                wave_tree_sum3_desc(err * g0, err * g1, err * err, G[3], G[4], G[5]);
-                wave_tree_sum3_desc(g0 * R, g1 * R, g0, G[6], G[7], G[8]);
-                wave_tree_sum3_desc(g1, R * R, R, G[9], G[10], G[11]);
-                wave_tree_sum3_desc(err * R, err, 0.0, G[12], G[13], G[14]);
+                double n_out = 0.0;
+                if constexpr (kRobust) {
+                    // Huber's weight of the pixel: every leaf is w x, x the plain
+                    // form's leaf; the cost's is twice the Huber function
+                    const double r = fabs(err);
+                    const bool out = r > hk;
+                    const double wt = out ? hk / r : 1.0;
+                    const double rho = out ? hk * (2.0 * r - hk) : err * err;
+                    n_out = (double)__popcll(__ballot(out));
+                    wave_tree_sum3_desc(wt * (g0 * g0), wt * (g0 * g1), wt * (g1 * g1), G[0], G[1], G[2]);
+                    wave_tree_sum3_desc(wt * (err * g0), wt * (err * g1), rho, G[3], G[4], G[5]);
+                    wave_tree_sum3_desc(wt * (g0 * R), wt * (g1 * R), wt * g0, G[6], G[7], G[8]);
+                    wave_tree_sum3_desc(wt * g1, wt * (R * R), wt * R, G[9], G[10], G[11]);
+                    wave_tree_sum3_desc(wt * (err * R), wt * err, wt, G[12], G[13], G[14]);
+                    mass = G[14];
+                } else {
+                    wave_tree_sum3_desc(g0 * g0, g0 * g1, g1 * g1, G[0], G[1], G[2]);
+                    wave_tree_sum3_desc(err * g0, err * g1, err * err, G[3], G[4], G[5]);
+                    wave_tree_sum3_desc(g0 * R, g1 * R, g0, G[6], G[7], G[8]);
+                    wave_tree_sum3_desc(g1, R * R, R, G[9], G[10], G[11]);
+                    wave_tree_sum3_desc(err * R, err, 0.0, G[12], G[13], G[14]);
+                }
                 const double J0a = pick6(J0, ta), J0b = pick6(J0, tb), J1a = pick6(J1, ta), J1b = pick6(J1, tb);
                 const double th = (G[0] * (J0a * J0b) + G[1] * (J0a * J1b + J1a * J0b)) + G[2] * (J1a * J1b);
                 const double tbv = G[3] * J0a + G[4] * J1a;
@@ -485,9 +562,12 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
                        : lane == 41 ? G[11]
                        : lane == 42 ? -G[12]
                                     : -G[13];
+                if constexpr (kRobust) term = lane == 44 ? G[14] : lane == 45 ? n_out : term;
                 cnt += 1;
             }
             if (lane < kBrTerms) L.acc[p][lane] = term;
+            if constexpr (kRobust)
+                if (lane == 0 && p < c) args.weights[first + p] = mass;
         }
         if (lane == 0) L.cnt[wave] = cnt;
         lds_tree(L, pc, tid);
@@ -504,13 +584,13 @@ __global__ __launch_bounds__(kBrLanes) void bright_pass_kernel(BrightArgs a, int
 }  // namespace
 
 size_t bright_scratch_bytes() {
-    return 2 * (size_t)kBrMaxTiles * kBrTerms * 8 + 2 * (size_t)kBrMaxTiles * 4 + 2 * (size_t)kBrightState * 8;
+    return 2 * (size_t)kBrMaxTiles * kBrightTerms * 8 + 2 * (size_t)kBrMaxTiles * 4 + 2 * (size_t)kBrightState * 8;
 }
 
 void bright_scratch_at(BrightArgs& a, void* base) {
     char* b = (char*)base;
     a.part = (double*)b;
-    b += 2 * (size_t)kBrMaxTiles * kBrTerms * 8;
+    b += 2 * (size_t)kBrMaxTiles * kBrightTerms * 8;
     a.state = (double*)b;
     b += 2 * (size_t)kBrightState * 8;
     a.good = (int*)b;
@@ -518,14 +598,44 @@ void bright_scratch_at(BrightArgs& a, void* base) {
 
 int bright_launches(int iterations) { return kLevels * (iterations + 1) + 1; }
 
-void launch_bright(BrightArgs a, hipStream_t stream) {
+namespace {
+
+// the canonical map tree's tiles; returns the grid
+int bright_tiles(BrightArgs& a) {
     const int n = a.n > 0 ? a.n : 0;
     a.tile = std::max(1, std::min(kBrMaxTile, (n + kBrMaxTiles - 1) / kBrMaxTiles));  // oracle_common.hpp map_tile
     a.n_tiles = (n + a.tile - 1) / a.tile;
-    const int grid = a.n_tiles > 0 ? a.n_tiles : 1, chain = bright_launches(a.iterations);
+    return a.n_tiles > 0 ? a.n_tiles : 1;
+}
+
+}  // namespace
+
+void launch_bright(BrightArgs a, hipStream_t stream) {
+    const int grid = bright_tiles(a), chain = bright_launches(a.iterations);
     for (int k = 0; k < chain; ++k) {
         const int last = k == chain - 1;
-        bright_pass_kernel<<<last ? 1 : grid, kBrLanes, 0, stream>>>(a, k, last);
+        bright_pass_kernel<false><<<last ? 1 : grid, kBrLanes, 0, stream>>>(a, k, last);
+    }
+}
+
+size_t robust_scratch_bytes() {
+    return 2 * (size_t)kBrMaxTiles * kRobustTerms * 8 + 2 * (size_t)kBrMaxTiles * 4 + 2 * (size_t)kBrightState * 8;
+}
+
+void robust_scratch_at(RobustArgs& a, void* base) {
+    char* b = (char*)base;
+    a.b.part = (double*)b;
+    b += 2 * (size_t)kBrMaxTiles * kRobustTerms * 8;
+    a.b.state = (double*)b;
+    b += 2 * (size_t)kBrightState * 8;
+    a.b.good = (int*)b;
+}
+
+void launch_robust(RobustArgs a, hipStream_t stream) {
+    const int grid = bright_tiles(a.b), chain = bright_launches(a.b.iterations);
+    for (int k = 0; k < chain; ++k) {
+        const int last = k == chain - 1;
+        bright_pass_kernel<true><<<last ? 1 : grid, kBrLanes, 0, stream>>>(a, k, last);
     }
 }
 
@@ -562,28 +672,55 @@ int viso_ctx::bright_frame(int last, int cur, int li) {
     a.info = bright_info();
     {
         TimedRegion t(timing, VISO_KERNEL_BRIGHT, stream);
-        launch_bright(a, stream);
+        if (robust_on()) {
+            // the robust form: its own scratch, report, weights, log and
+            // counters; the brightness report, log and counters as ever
+            RobustArgs r{};
+            r.b = a;
+            robust_scratch_at(r, robust_buf.ptr);
+            r.huber_k = robust_k;
+            r.weights = robust_weights();
+            r.report = robust_report();
+            r.rlog = robust_log();
+            r.info = robust_info();
+            robust_wn = n_map;
+            launch_robust(r, stream);
+        } else {
+            launch_bright(a, stream);
+        }
     }
     VISO_HIP_CHECK(hipGetLastError());
     return VISO_OK;
 }
 
-extern "C" {
+int viso_ctx::robust_ensure() {
+    if (!bright_on() || !robust_on() || robust_buf.ptr) return VISO_OK;
+    VISO_HIP_CHECK(hipSetDevice(device));
+    const size_t head = robust_head() + 8 * (size_t)kMaxMapPoints;
+    const size_t bytes = head + 16 * (size_t)std::max(p.max_poses, 1);
+    if (int rc = robust_buf.ensure(bytes)) return rc;
+    VISO_HIP_CHECK(hipMemsetAsync(robust_buf.ptr, 0, head, stream));
+    VISO_HIP_CHECK(hipMemsetAsync((char*)robust_buf.ptr + head, 0xff, bytes - head, stream));  // NaN rows
+    return VISO_OK;
+}
 
-int viso_track_affine(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_pyr, int32_t width, int32_t height,
-                      const double* points, int32_t n_points, const double* pose_last12, const double* seed12,
-                      int32_t iterations, double* pose_out12, double* report24) {
-    if (!c || !last_pyr || !cur_pyr || width < 64 || height < 64 || width > kMaxWidth || height > kMaxWidth ||
-        n_points < 0 || n_points > kMaxMapPoints || (n_points > 0 && !points) || !pose_last12 || !seed12 ||
-        iterations < 1 || iterations > 20 || !pose_out12 || !report24)
-        return VISO_ERR_ARG;
+namespace {
+
+// viso_track_affine (huber_k = 0) and viso_track_robust behind their argument
+// checks: the stage on host data through the frame path's launches.
+int track_stage(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_pyr, int width, int height,
+                const double* points, int n_points, const double* pose_last12, const double* seed12, int iterations,
+                double huber_k, double* pose_out12, double* report, double* weights) {
+    const bool robust = huber_k > 0.0;
+    const int n_report = robust ? kRobustReport : kBrightReport;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     VISO_HIP_CHECK(hipSetDevice(c->device));
     const PyrGeom g = make_geom(width, height);
     Bump b;
     const size_t o_l = b.take(g.bytes), o_c = b.take(g.bytes), o_p = b.take(24 * (size_t)std::max(n_points, 1)),
-                 o_pl = b.take(96), o_s = b.take(96), o_po = b.take(96), o_r = b.take(8 * kBrightReport),
-                 o_x = b.take(bright_scratch_bytes());
+                 o_pl = b.take(96), o_s = b.take(96), o_po = b.take(96), o_r = b.take(8 * n_report),
+                 o_x = b.take(robust ? robust_scratch_bytes() : bright_scratch_bytes()),
+                 o_w = b.take(robust ? 8 * (size_t)std::max(n_points, 1) : 0);
     if (int rc = c->scratch_a.ensure(b.off)) return rc;
     char* base = (char*)c->scratch_a.ptr;
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_l, last_pyr, g.bytes, hipMemcpyHostToDevice, c->stream));
@@ -605,17 +742,122 @@ int viso_track_affine(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_p
     a.pose_last = (const double*)(base + o_pl);
     a.seed = (const double*)(base + o_s);
     a.iterations = iterations;
-    bright_scratch_at(a, base + o_x);
     a.pose_out = (double*)(base + o_po);
-    a.report = (double*)(base + o_r);
     a.log_index = -1;
     {
         TimedRegion t(c->timing, VISO_KERNEL_BRIGHT, c->stream);
-        launch_bright(a, c->stream);
+        if (robust) {
+            RobustArgs r{};
+            r.b = a;
+            robust_scratch_at(r, base + o_x);
+            r.huber_k = huber_k;
+            r.weights = (double*)(base + o_w);
+            r.report = (double*)(base + o_r);
+            launch_robust(r, c->stream);
+        } else {
+            bright_scratch_at(a, base + o_x);
+            a.report = (double*)(base + o_r);
+            launch_bright(a, c->stream);
+        }
     }
     VISO_HIP_CHECK(hipGetLastError());
-    VISO_HIP_CHECK(hipMemcpyAsync(pose_out12, a.pose_out, 96, hipMemcpyDeviceToHost, c->stream));
-    VISO_HIP_CHECK(hipMemcpyAsync(report24, a.report, 8 * kBrightReport, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(pose_out12, base + o_po, 96, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(report, base + o_r, 8 * (size_t)n_report, hipMemcpyDeviceToHost, c->stream));
+    if (robust && weights && n_points > 0)
+        VISO_HIP_CHECK(hipMemcpyAsync(weights, base + o_w, 8 * (size_t)n_points, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VISO_OK;
+}
+
+bool track_args_ok(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_pyr, int width, int height,
+                   const double* points, int n_points, const double* pose_last12, const double* seed12, int iterations,
+                   double* pose_out12, double* report) {
+    return c && last_pyr && cur_pyr && width >= 64 && height >= 64 && width <= kMaxWidth && height <= kMaxWidth &&
+           n_points >= 0 && n_points <= kMaxMapPoints && (n_points == 0 || points) && pose_last12 && seed12 &&
+           iterations >= 1 && iterations <= 20 && pose_out12 && report;
+}
+
+// viso_set_robust's and viso_track_robust's k: finite, 0 < k <= 1e300
+bool huber_k_ok(double k) { return k > 0.0 && k <= 1e300; }
+
+}  // namespace
+
+extern "C" {
+
+int viso_track_affine(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_pyr, int32_t width, int32_t height,
+                      const double* points, int32_t n_points, const double* pose_last12, const double* seed12,
+                      int32_t iterations, double* pose_out12, double* report24) {
+    if (!track_args_ok(c, last_pyr, cur_pyr, width, height, points, n_points, pose_last12, seed12, iterations,
+                       pose_out12, report24))
+        return VISO_ERR_ARG;
+    return track_stage(c, last_pyr, cur_pyr, width, height, points, n_points, pose_last12, seed12, iterations, 0.0,
+                       pose_out12, report24, nullptr);
+}
+
+int viso_track_robust(viso_ctx* c, const uint8_t* last_pyr, const uint8_t* cur_pyr, int32_t width, int32_t height,
+                      const double* points, int32_t n_points, const double* pose_last12, const double* seed12,
+                      int32_t iterations, double huber_k, double* pose_out12, double* report28, double* weights) {
+    if (!track_args_ok(c, last_pyr, cur_pyr, width, height, points, n_points, pose_last12, seed12, iterations,
+                       pose_out12, report28) ||
+        !huber_k_ok(huber_k))
+        return VISO_ERR_ARG;
+    return track_stage(c, last_pyr, cur_pyr, width, height, points, n_points, pose_last12, seed12, iterations, huber_k,
+                       pose_out12, report28, weights);
+}
+
+int viso_set_robust(viso_ctx* c, double huber_k) {
+    if (!c || !(huber_k == 0.0 || huber_k_ok(huber_k))) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    c->robust_k = huber_k;
+    return c->robust_ensure();
+}
+
+int viso_get_robust(viso_ctx* c, int64_t info[8]) {
+    if (!c || !info) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (c->robust_buf.ptr) {
+        VISO_HIP_CHECK(hipSetDevice(c->device));
+        VISO_HIP_CHECK(hipMemcpyAsync(info, c->robust_info(), 64, hipMemcpyDeviceToHost, c->stream));
+        VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    info[0] = c->robust_on() ? 1 : 0;
+    for (int k = 4; k < 8; ++k) info[k] = 0;
+    return VISO_OK;
+}
+
+int viso_get_robust_report(viso_ctx* c, double report[28]) {
+    if (!c || !report) return VISO_ERR_ARG;
+    if (!c->robust_buf.ptr) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipMemcpyAsync(report, c->robust_report(), 8 * kRobustReport, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VISO_OK;
+}
+
+int viso_get_robust_weights(viso_ctx* c, double* w, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (!c->robust_buf.ptr) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    const size_t total = (size_t)c->robust_wn;
+    if (n) *n = total;
+    const size_t m = std::min(cap, total);
+    if (m > 0 && w) VISO_HIP_CHECK(hipMemcpyAsync(w, c->robust_weights(), 8 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VISO_OK;
+}
+
+int viso_get_robust_log(viso_ctx* c, double* rows, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (!c->robust_buf.ptr) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    const size_t total = std::min((size_t)c->n_poses, (size_t)std::max(c->p.max_poses, 0));
+    if (n) *n = total;
+    const size_t m = std::min(cap, total);
+    if (m > 0 && rows) VISO_HIP_CHECK(hipMemcpyAsync(rows, c->robust_log(), 16 * m, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VISO_OK;
 }
@@ -632,7 +874,7 @@ int viso_set_brightness(viso_ctx* c, int32_t iterations) {
         VISO_HIP_CHECK(hipMemsetAsync((char*)c->bright_buf.ptr + head, 0xff, bytes - head, c->stream));  // NaN rows
     }
     c->bright_iterations = iterations;
-    return VISO_OK;
+    return c->robust_ensure();  // (viso_set_robust ahead of this call)
 }
 
 int viso_get_brightness(viso_ctx* c, int64_t info[8]) {

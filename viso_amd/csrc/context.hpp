@@ -538,6 +538,25 @@ struct viso_ctx {
     // the tracking frame cur from the frame `last` (li: its pose-log index)
     int bright_frame(int last, int cur, int li);
 
+    // robust tracking (viso_set_robust; bright.hip): while
+    // robust_k > 0 and the brightness mode is on, bright_frame runs the chain's
+    // robust form with this k.  robust_buf is null until both are on for the
+    // first time: the robust chain's scratch, the counters of viso_get_robust
+    // (8 x int64), the last report (28), the last frame's weight mass per map
+    // point (kMaxMapPoints), the log (max_poses x 2, NaN until written).
+    // robust_wn: the map's size when the last robust frame was tracked
+    double robust_k = 0.0;
+    viso::DevBuf robust_buf;
+    int robust_wn = 0;
+    bool robust_on() const { return robust_k > 0.0; }
+    size_t robust_head() const { return ((viso::robust_scratch_bytes() + 255) & ~(size_t)255) + 512; }
+    long long* robust_info() const { return (long long*)((char*)robust_buf.ptr + robust_head() - 512); }
+    double* robust_report() const { return (double*)(robust_info() + 8); }
+    double* robust_weights() const { return (double*)((char*)robust_buf.ptr + robust_head()); }
+    double* robust_log() const { return robust_weights() + viso::kMaxMapPoints; }
+    // allocates robust_buf once both modes are on
+    int robust_ensure();
+
     // rectification (viso_set_rectify; rectify.hip): camera 0
     // is the left (or only) camera, camera 1 the right one; model 0 = off.  A
     // rectified frame's level 0 is written into its own slot (never

@@ -227,7 +227,7 @@ void viso_ctx::release() {
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
                       &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rseed_buf, &rect_map[0],
-                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf};
+                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf, &robust_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -1538,6 +1538,8 @@ int viso_ctx::on_new_frame(int cur) {
                     // (a lost frame has no brightness row, as it has no frame-log row)
                     if (bright && dpend_log >= 0)
                         VISO_HIP_CHECK(hipMemsetAsync(bright_log() + 4 * (size_t)dpend_log, 0xff, 32, stream));
+                    if (bright && robust_on() && dpend_log >= 0)
+                        VISO_HIP_CHECK(hipMemsetAsync(robust_log() + 2 * (size_t)dpend_log, 0xff, 16, stream));
                     if (int rc = reloc_lost_frame(cur, dpend_log)) return rc;
                     break;
                 }

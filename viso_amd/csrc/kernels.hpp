@@ -532,6 +532,24 @@ void bright_scratch_at(BrightArgs& a, void* base);
 int bright_launches(int iterations);  // 4 (iterations + 1) + 1
 void launch_bright(BrightArgs a, hipStream_t stream);
 
+// The robust form of the chain (viso_track_robust, viso_set_robust; DESIGN.md
+// §23): a Huber weight per patch pixel, 46 sums per pass.  b is the plain
+// form's arguments with part sized for kRobustTerms (robust_scratch_at) and
+// report (the plain 24 columns) null where nobody reads them.
+constexpr int kRobustReport = 28;  // doubles
+constexpr int kRobustTerms = 46;   // + sum w, the count of pixels with |e| > k
+struct RobustArgs {
+    BrightArgs b;
+    double huber_k;
+    double* weights;           // n: every pass writes its points' sum w (0: not good)
+    double* report;            // kRobustReport
+    double* rlog;              // the robust log (2 doubles per pose index): row b.log_index, or null
+    long long* info;           // viso_get_robust's counters, or null
+};
+size_t robust_scratch_bytes();
+void robust_scratch_at(RobustArgs& a, void* base);
+void launch_robust(RobustArgs a, hipStream_t stream);
+
 // ---------------------------------------------------------------- direct pose
 constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of

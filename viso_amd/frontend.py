@@ -339,6 +339,32 @@ class Viso(FrameHandler):
         """The last frame's report (24,), as Context.track_affine returns it."""
         return self.ctx.brightness_report()
 
+    def set_robust(self, huber_k: float = 9.0) -> None:
+        """Robust tracking (viso_set_robust): every frame the brightness chain
+        tracks (set_brightness) weights each patch pixel by Huber's rule with
+        this k (grey levels), so occluders and wrong map points stop bending the
+        pose.  huber_k 0 = off; no effect while set_brightness is off."""
+        self.ctx.set_robust(huber_k)
+
+    def robust(self) -> np.ndarray:
+        """viso_get_robust: int64[8] = on, frames tracked robustly, then of the
+        last such frame: its down-weighted pixels, its level-0 n, 0..."""
+        return self.ctx.get_robust()
+
+    def robust_report(self) -> np.ndarray:
+        """The last robust frame's report (28,), as Context.track_robust returns it."""
+        return self.ctx.robust_report()
+
+    def robust_weights(self) -> np.ndarray:
+        """The last robust frame's weight mass per map point (64 = every patch
+        pixel at full weight), in the map's order when that frame was tracked."""
+        return self.ctx.robust_weights()
+
+    def robust_log(self) -> np.ndarray:
+        """One row per pose: mean weight, down-weighted pixels (NaN for frames
+        not tracked robustly and for lost frames)."""
+        return self.ctx.robust_log()
+
     def frame_status(self) -> np.ndarray:
         """viso_get_frame_status: one byte per pose: 0 tracked, 1 tracked with
         a bad verdict, 2 lost (the held pose), 3 recovered."""
