@@ -447,6 +447,27 @@ public:
         return r;
     }
 
+    // Illumination-invariant LK alignment (viso_set_lk_illum): a per-patch
+    // gain and offset are projected out of the warped alignment; runs while
+    // SetLkWarp is on.  mode 0 = off.
+    void SetLkIllum(int mode, double max_gain = 4.0) {
+        check(viso_set_lk_illum(ctx_, mode, max_gain), "viso_set_lk_illum");
+    }
+    // viso_get_lk_illum's info[8]
+    std::array<int64_t, 8> LkIllum() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_lk_illum(ctx_, info.data()), "viso_get_lk_illum");
+        return info;
+    }
+    // the last frame's (gain, offset) rows, 2 per point
+    std::vector<double> LkIllumRows() const {
+        size_t n = 0;
+        check(viso_get_lk_illum_rows(ctx_, nullptr, 0, &n), "viso_get_lk_illum_rows");
+        std::vector<double> go(2 * n);
+        if (n) check(viso_get_lk_illum_rows(ctx_, go.data(), n, &n), "viso_get_lk_illum_rows");
+        return go;
+    }
+
     // Depth seeds (viso_set_depth_seeds): every corner of a new keyframe that
     // the map does not cover becomes a seed; every tracking frame searches the
     // seed's epipolar segment and narrows its inverse depth; every

@@ -596,6 +596,42 @@ int viso_lk_align_warped(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf
                          uint8_t* success, double* uv_before, double* uv_after, double* A4, int8_t* shift,
                          uint8_t* status);
 
+/* Illumination-invariant LK alignment (the repo's own spec; no
+ * reference counterpart): a form of the warped alignment that removes a
+ * per-patch affine brightness change (gain, offset) between the keyframe
+ * patch and the current image, by the project-out form of the inverse-
+ * compositional iterations: per level the Jacobian is projected off
+ * span{1, T}, H stays constant, and the cost is the energy of the residual
+ * with its mean and its component along the centred template removed.  A
+ * level whose template is flat (sum of squared deviations < 64) is skipped as
+ * a level whose taps leave the reference level.  After level 0 an aligned
+ * point's gain has to lie in [1 / max_gain, max_gain]; one outside gets
+ * success 0 and status 3 (uv_after stays where the iterations ended).  fp64 in
+ * both precision modes.  It runs while viso_set_lk_warp is on; with the warp
+ * off the mode is kept, inert (nothing is launched or allocated for it).
+ * mode 0 = off (default): nothing changes.  mode: 0 or 1; max_gain finite, in
+ * [1.5, 16] (4 suggested); anything else VISO_ERR_ARG.  May be called while
+ * tracking (pending work is settled first).  Frames are timed under
+ * VISO_KERNEL_LKWARP. */
+int viso_set_lk_illum(viso_ctx* ctx, int32_t mode, double max_gain);
+/* info = {mode, frames aligned with the mode on, then of the last frame's row:
+ * points paired, aligned (success), points whose gain was out of bounds
+ * (status 3), 0, 0, 0}.  All 0 while the mode or the warp is off. */
+int viso_get_lk_illum(viso_ctx* ctx, int64_t info[8]);
+/* The last frame's gain/offset rows (n x 2 doubles): the last accepted
+ * level-0 iteration's (gain, offset), current = gain * keyframe + offset; NaN
+ * where there was none.  The first min(cap, n) are written; *n = the row's
+ * points.  VISO_ERR_STATE while the mode is off or the warp is off. */
+int viso_get_lk_illum_rows(viso_ctx* ctx, double* gain_offset2, size_t cap, size_t* n);
+/* Stage entry (parity tests): viso_lk_align_warped's arguments and outputs by
+ * the illumination-invariant form, plus max_gain and gain_offset (n x 2).  A4,
+ * shift, status and gain_offset may each be NULL. */
+int viso_lk_align_illum(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                        const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                        const double* points, int32_t n_points, double max_area_ratio, double max_gain,
+                        int32_t* pair_kf, uint8_t* success, double* uv_before, double* uv_after, double* A4,
+                        int8_t* shift, uint8_t* status, double* gain_offset);
+
 /* Depth seeds (the repo's own spec; no reference counterpart):
  * the map grows by an epipolar search over the frames after a keyframe.  A
  * seed is a corner (u, v) of keyframe h (level 0) with an inverse depth mu of

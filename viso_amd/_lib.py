@@ -133,6 +133,11 @@ SIGNATURES = {
     "viso_get_lk_warp_rows": [_vp, _vp, _vp, _vp, _sz, _vp],
     "viso_lk_align_warped": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _d, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp],
+    "viso_set_lk_illum": [_vp, _i32, _d],
+    "viso_get_lk_illum": [_vp, _vp],
+    "viso_get_lk_illum_rows": [_vp, _vp, _sz, _vp],
+    "viso_lk_align_illum": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _d, _d, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp],
     "viso_set_depth_seeds": [_vp, _i32, _i32, _i32, _d, _d, _d, _d, _i32, _d, _i32, _i32],
     "viso_get_depth_seeds": [_vp, _vp],
     "viso_get_depth_seed_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],

@@ -166,6 +166,34 @@ class Context:
                   _p(pk), _p(sc), _p(ub), _p(ua), _p(A), _p(sh), _p(st))
         return pk, sc, ub, ua, A, sh, st
 
+    def lk_align_illum(self, kf_pyrs, kf_poses, cur_pyr, cur_pose, width, height, points,
+                       max_area_ratio: float = 64.0, max_gain: float = 4.0, warp_rows: bool = True,
+                       gain_rows: bool = True):
+        """viso_lk_align_illum: ``lk_align_warped`` by the illumination-
+        invariant form (viso_set_lk_illum).  Returns (pair_kf, success,
+        uv_before, uv_after, A (n, 4), shift, status, gain_offset (n, 2));
+        with ``warp_rows`` / ``gain_rows`` false those outputs are passed as
+        NULL and returned as None."""
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple))
+                                   else kf_pyrs, dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        pk = np.zeros(n, np.int32)
+        sc = np.zeros(n, np.uint8)
+        ub = np.zeros((n, 2), np.float64)
+        ua = np.zeros((n, 2), np.float64)
+        A = np.zeros((n, 4), np.float64) if warp_rows else None
+        sh = np.zeros(n, np.int8) if warp_rows else None
+        st = np.zeros(n, np.uint8) if warp_rows else None
+        go = np.zeros((n, 2), np.float64) if gain_rows else None
+        cp = np.ascontiguousarray(cur_pose, dtype=np.float64).reshape(12)
+        opt = lambda a: None if a is None else _p(a)
+        _lib.call("viso_lk_align_illum", self.h, _p(kfp), _p(kposes), kposes.shape[0],
+                  _p(np.ascontiguousarray(cur_pyr)), _p(cp), width, height, _p(pts), n, float(max_area_ratio),
+                  float(max_gain), _p(pk), _p(sc), _p(ub), _p(ua), opt(A), opt(sh), opt(st), opt(go))
+        return pk, sc, ub, ua, A, sh, st, go
+
     # depth seeds (viso_depth_seeds_*; DESIGN.md §18).  Seed rows travel as a
     # dict: h (n,) int32, uv (n, 2), mu (n,), s2 (n,), cnt (n, 4) int32 =
     # (good, bad, lost, status).

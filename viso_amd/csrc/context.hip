@@ -369,21 +369,25 @@ int viso_direct_solve(viso_ctx* c, const double sums[28], int32_t n_good, const 
     return VISO_OK;
 }
 
-// viso_lk_align (warp == false) and viso_lk_align_warped: the same staging,
-// the batched kernel or the warped one
+// viso_lk_align (warp == false), viso_lk_align_warped and viso_lk_align_illum
+// (illum: the warped kernel's illumination-invariant form, whose warp rows
+// and gain/offset rows are optional outputs): the same staging, the batched
+// kernel or the warped one
 static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
                           const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
                           const double* points, int32_t n, int32_t* pair_kf, uint8_t* success,
                           double* uv_before, double* uv_after, bool warp, double max_area_ratio, double* A4,
-                          int8_t* shift, uint8_t* status) {
+                          int8_t* shift, uint8_t* status, bool illum = false, double max_gain = 0.0,
+                          double* gain_offset = nullptr) {
     if (!c || !kf_pyrs || !kf_poses || n_kf <= 0 || n_kf > kMaxKeyframes || !cur_pyr || !cur_pose ||
         n < 0)
         return VISO_ERR_ARG;
     if (warp && !(max_area_ratio >= 4.0 && max_area_ratio <= 64.0)) return VISO_ERR_ARG;
+    if (illum && !(max_gain >= 1.5 && max_gain <= 16.0)) return VISO_ERR_ARG;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     if (n == 0) return VISO_OK;
     if (!points || !pair_kf || !success || !uv_before || !uv_after) return VISO_ERR_ARG;
-    if (warp && (!A4 || !shift || !status)) return VISO_ERR_ARG;
+    if (warp && !illum && (!A4 || !shift || !status)) return VISO_ERR_ARG;
     VISO_HIP_CHECK(hipSetDevice(c->device));
     PyrGeom g = make_geom(width, height);
     Bump b;
@@ -393,6 +397,7 @@ static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_
            o_ua = b.take(16 * (size_t)n);
     const size_t o_wa = warp ? b.take(32 * (size_t)n) : 0, o_ws = warp ? b.take((size_t)n) : 0,
                  o_wt = warp ? b.take((size_t)n) : 0;
+    const size_t o_go = illum ? b.take(16 * (size_t)n) : 0;
     int rc = c->scratch_a.ensure(b.off);
     if (rc) return rc;
     char* base = (char*)c->scratch_a.ptr;
@@ -427,6 +432,11 @@ static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_
         a.warp_A = (double*)(base + o_wa);
         a.warp_shift = (int8_t*)(base + o_ws);
         a.warp_status = (uint8_t*)(base + o_wt);
+        if (illum) {
+            a.illum = 1;
+            a.illum_max_gain = max_gain;
+            a.illum_go = (double*)(base + o_go);
+        }
         TimedRegion t(c->timing, VISO_KERNEL_LKWARP, c->stream);
         launch_lk_warp(a, c->stream);
     } else {
@@ -435,10 +445,12 @@ static int lk_align_stage(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_
     }
     VISO_HIP_CHECK(hipGetLastError());
     if (warp) {
-        VISO_HIP_CHECK(hipMemcpyAsync(A4, base + o_wa, 32 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        VISO_HIP_CHECK(hipMemcpyAsync(shift, base + o_ws, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        VISO_HIP_CHECK(hipMemcpyAsync(status, base + o_wt, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (A4) VISO_HIP_CHECK(hipMemcpyAsync(A4, base + o_wa, 32 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (shift) VISO_HIP_CHECK(hipMemcpyAsync(shift, base + o_ws, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (status) VISO_HIP_CHECK(hipMemcpyAsync(status, base + o_wt, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     }
+    if (illum && gain_offset)
+        VISO_HIP_CHECK(hipMemcpyAsync(gain_offset, base + o_go, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(pair_kf, base + o_pk, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(success, base + o_s, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(uv_before, base + o_ub, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -462,6 +474,15 @@ int viso_lk_align_warped(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_p
                          uint8_t* status) {
     return lk_align_stage(c, kf_pyrs, kf_poses, n_kf, cur_pyr, cur_pose, width, height, points, n, pair_kf, success,
                           uv_before, uv_after, true, max_area_ratio, A4, shift, status);
+}
+
+int viso_lk_align_illum(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                        const uint8_t* cur_pyr, const double cur_pose[12], int32_t width, int32_t height,
+                        const double* points, int32_t n, double max_area_ratio, double max_gain, int32_t* pair_kf,
+                        uint8_t* success, double* uv_before, double* uv_after, double* A4, int8_t* shift,
+                        uint8_t* status, double* gain_offset) {
+    return lk_align_stage(c, kf_pyrs, kf_poses, n_kf, cur_pyr, cur_pose, width, height, points, n, pair_kf, success,
+                          uv_before, uv_after, true, max_area_ratio, A4, shift, status, true, max_gain, gain_offset);
 }
 
 }  // extern "C"

@@ -438,6 +438,21 @@ struct viso_ctx {
     uint8_t* warp_status() const {
         return (uint8_t*)warp_buf.ptr + (size_t)33 * viso::kLkBatch * viso::kMaxMapPoints;
     }
+    // illumination-invariant LK alignment (viso_set_lk_illum; track.hip
+    // lk_warp_kernel<true>): a form of the warped kernel, so
+    // with the warp off the mode is kept, inert.  illum_buf: the gain/offset
+    // rows, kLkBatch x kMaxMapPoints x 2 doubles, allocated when both modes
+    // are first on (ensure_illum_rows) and freed with the warp rows.
+    // illum_rows_valid: the last LK batch ran the form
+    int illum_mode = 0;
+    double illum_max_gain = 0.0;
+    int64_t illum_frames = 0;
+    bool illum_rows_valid = false;
+    viso::DevBuf illum_buf;
+    bool illum_on() const { return illum_mode != 0 && warp_on(); }
+    int ensure_illum_rows() {
+        return illum_buf.ptr ? 0 : illum_buf.ensure((size_t)16 * viso::kLkBatch * viso::kMaxMapPoints);
+    }
     // depth seeds (viso_set_depth_seeds; depthseed.hip): every keyframe
     // creation adds a seed set (the cell winners of its corners in the cells
     // the map leaves unmarked), every tracking frame updates every seed at its

@@ -227,7 +227,8 @@ void viso_ctx::release() {
                       &bg_buf, &lk_pair, &lk_succ, &lk_before, &lk_after, &lk_tmpl, &lk_tmpl_h,
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
                       &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rseed_buf, &rect_map[0],
-                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf, &robust_buf};
+                      &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf, &robust_buf,
+                      &illum_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -595,6 +596,13 @@ int viso_ctx::flush_lk_frames(hipStream_t ls, bool keep_last) {
         a.warp_A = warp_A();
         a.warp_shift = warp_shift();
         a.warp_status = warp_status();
+        if (illum_on()) {  // the illumination-invariant form
+            if (int rc = ensure_illum_rows()) return rc;
+            a.illum = 1;
+            a.illum_max_gain = illum_max_gain;
+            a.illum_go = (double*)illum_buf.ptr;
+            illum_frames += a.n_frames;
+        }
         TimedRegion t(timing, VISO_KERNEL_LKWARP, ls);
         launch_lk_warp(a, ls);
         warp_frames += a.n_frames;
@@ -607,6 +615,7 @@ int viso_ctx::flush_lk_frames(hipStream_t ls, bool keep_last) {
     }
     VISO_HIP_CHECK(hipGetLastError());
     warp_rows_valid = warp;
+    illum_rows_valid = a.illum != 0;
     if (int rc = count_lk(lk_pending, ls)) return rc;
     lk_last_rows = a.n_frames;
     lk_last_pts = n_map;  // a later keyframe insertion grows n_map, not these rows
@@ -1968,6 +1977,11 @@ int viso_set_lk_warp(viso_ctx* c, int32_t mode, double max_area_ratio) {
             if (int rc = c->warp_buf.ensure((size_t)34 * kLkBatch * kMaxMapPoints)) return rc;
             c->warp_rows_valid = false;
             c->warp_frames = 0;
+            if (c->illum_mode) {  // a kept viso_set_lk_illum comes into force
+                if (int rc = c->ensure_illum_rows()) return rc;
+                c->illum_rows_valid = false;
+                c->illum_frames = 0;
+            }
         }
         c->warp_ratio = max_area_ratio;
     } else if (c->warp_on()) {
@@ -1975,10 +1989,90 @@ int viso_set_lk_warp(viso_ctx* c, int32_t mode, double max_area_ratio) {
         VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
         VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
         c->warp_buf.release();
+        c->illum_buf.release();
         c->warp_rows_valid = false;
+        c->illum_rows_valid = false;
         c->warp_ratio = 0.0;
     }
     c->warp_mode = mode;
+    return VISO_OK;
+}
+
+// Illumination-invariant LK alignment (track.hip lk_warp_kernel<true>;
+// DESIGN.md §24): a form of the warped kernel.  With the warp off the mode is
+// kept, inert: nothing is launched or allocated for it.
+int viso_set_lk_illum(viso_ctx* c, int32_t mode, double max_gain) {
+    if (!c || (mode != 0 && mode != 1) || (mode == 1 && !(max_gain >= 1.5 && max_gain <= 16.0)))
+        return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    if (mode == 1) {
+        if (!c->illum_mode) {
+            if (c->warp_on())
+                if (int rc = c->ensure_illum_rows()) return rc;
+            c->illum_rows_valid = false;
+            c->illum_frames = 0;
+        }
+        c->illum_max_gain = max_gain;
+    } else if (c->illum_mode) {
+        // the last batch of the form may still run on the side stream
+        VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+        VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->illum_buf.release();
+        c->illum_rows_valid = false;
+        c->illum_max_gain = 0.0;
+    }
+    c->illum_mode = mode;
+    return VISO_OK;
+}
+
+// the last row's points when that row ran the illumination-invariant form
+static size_t illum_row_points(const viso_ctx* c) {
+    return (c->illum_on() && c->illum_rows_valid && c->warp_rows_valid && c->ran_tracking && c->lk_last_rows > 0)
+               ? (size_t)c->lk_last_pts
+               : 0;
+}
+
+int viso_get_lk_illum_rows(viso_ctx* c, double* gain_offset2, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (!c->illum_on()) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+    const size_t pts = illum_row_points(c);
+    const size_t m = std::min(cap, pts);
+    const size_t o = (size_t)std::max(c->lk_last_rows - 1, 0) * kMaxMapPoints;
+    if (m > 0 && gain_offset2)
+        VISO_HIP_CHECK(hipMemcpyAsync(gain_offset2, (double*)c->illum_buf.ptr + 2 * o, 16 * m, hipMemcpyDeviceToHost,
+                                      c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (n) *n = pts;
+    return VISO_OK;
+}
+
+int viso_get_lk_illum(viso_ctx* c, int64_t info[8]) {
+    if (!c || !info) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (!c->illum_on()) return VISO_OK;
+    info[0] = c->illum_mode;
+    info[1] = c->illum_frames;
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->lk_stream));
+    const size_t m = illum_row_points(c);
+    if (m == 0) return VISO_OK;
+    const size_t o = (size_t)(c->lk_last_rows - 1) * kMaxMapPoints;
+    std::vector<int32_t> pk(m);
+    std::vector<uint8_t> sc(m), st(m);
+    VISO_HIP_CHECK(hipMemcpyAsync(pk.data(), (int32_t*)c->lk_pair.ptr + o, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(sc.data(), (uint8_t*)c->lk_succ.ptr + o, m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipMemcpyAsync(st.data(), c->warp_status() + o, m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < m; ++i) {
+        info[2] += pk[i] >= 0;
+        info[3] += sc[i] != 0;
+        info[4] += (st[i] & 15) == 3;
+    }
     return VISO_OK;
 }
 

@@ -136,6 +136,14 @@ struct LkAlignArgs {
     double* warp_A = nullptr;
     int8_t* warp_shift = nullptr;
     uint8_t* warp_status = nullptr;
+    // illumination-invariant form of the warped alignment (viso_set_lk_illum;
+    // DESIGN.md §24): lk_warp_kernel<true>.  illum_max_gain bounds the level-0
+    // gain to [1 / max_gain, max_gain]; illum_go (optional): per point the
+    // last accepted level-0 iteration's (gain, offset), NaN where none, laid
+    // out as the outputs above
+    int illum = 0;
+    double illum_max_gain = 0.0;
+    double* illum_go = nullptr;
 };
 void launch_lk_align(const LkAlignArgs& a, hipStream_t stream);
 // LK alignment with every keyframe patch warped into the current view by the

@@ -383,6 +383,78 @@ __device__ inline LkResult lk_iterate(const LkTemplate& t, int w1, int h1,
     return {dx, dy, succ, iter};
 }
 
+// The per-level template of the illumination-invariant form (viso_set_lk_illum;
+// DESIGN.md §24): the template T with its mean m, Tc = T - m and stt = sum Tc
+// Tc, and the Jacobian projected off span{1, T}: P = (J - mean J) - c Tc.
+// (i00 .. i11): the inverse of H = sum P P^T.
+struct LkIllumTemplate {
+    double T, Tc, P0, P1;
+    double m, stt;
+    double i00, i01, i10, i11;
+};
+
+struct LkIllumResult {
+    double dx, dy;
+    bool succ;
+    bool any;       // an iteration was accepted: se, ste are its sums
+    double se, ste;
+};
+
+// lk_iterate<100, false>'s GN iterations with a per-patch gain and offset
+// projected out of the residual: because P is orthogonal to 1
+// and T, B needs no projected residual, and the cost is the projected
+// residual's energy by subtraction — still one reduction latency (two
+// independent three-slot trees) per iteration.
+__device__ inline LkIllumResult lk_iterate_illum(const LkIllumTemplate& t, int w1, int h1,
+                                                 const uint8_t* __restrict__ img2, int w2, int h2, double cur_x,
+                                                 double cur_y, double bx, double by, double thresh, Window win) {
+    constexpr int MAXIT = 100;
+    const double hp = 4.0;
+    bx = uniform_f64(bx);
+    by = uniform_f64(by);
+    double dx = 0.0, dy = 0.0;
+    const double i00 = uniform_f64(t.i00), i01 = uniform_f64(t.i01), i10 = uniform_f64(t.i10),
+                 i11 = uniform_f64(t.i11);
+    const double stt = uniform_f64(t.stt);
+    // the bounds test lane-parallel, as in lk_iterate
+    const int lq = threadIdx.x & 3;
+    const double b_l = (lq & 1) ? by : bx;
+    const double off_l = (lq & 2) ? hp : -hp;
+    const double lim_l = (double)((lq & 1) ? h1 : w1);
+    double lastCost = 0;
+    double se_acc = 0, ste_acc = 0;
+    bool succ = true, any = false;
+    TapCache tc{INT_MIN, INT_MIN, 0u};
+    for (int iter = 0; iter < MAXIT; ++iter) {
+        const double q = (b_l + ((lq & 1) ? dy : dx)) + off_l;
+        if (__builtin_amdgcn_ballot_w64(!(q >= 0 && q < lim_l)) != 0) {
+            succ = false;
+            break;
+        }
+        const double smp = sample_win_cached<true>(img2, w2, h2, cur_x + dx, cur_y + dy, win, tc);
+        const double e = t.T - smp;
+        double B0, B1, see, se, ste, unused;
+        wave_tree_sum3_desc(-t.P0 * e, -t.P1 * e, e * e, B0, B1, see);
+        wave_tree_sum3_desc(e, t.Tc * e, 0.0, se, ste, unused);
+        const double cost = (see - (se * se) * (1.0 / 64.0)) - (ste * ste) / stt;
+        const double u0 = i00 * B0 + i01 * B1;
+        const double u1 = i10 * B0 + i11 * B1;
+        if (isnan(u0)) {
+            succ = false;
+            break;
+        }
+        if (iter > 0 && cost > lastCost) break;
+        dx += u0;
+        dy += u1;
+        lastCost = cost;
+        succ = !(lastCost > thresh);
+        any = true;
+        se_acc = se;
+        ste_acc = ste;
+    }
+    return {dx, dy, succ, any, se_acc, ste_acc};
+}
+
 // Tolerance mode (VISO_PRECISION_FAST) GN iterations of one LKAlignment
 // level: the same control flow (bounds test on ref coords + d, NaN / cost-
 // increase stops, success = last accepted cost <= thresh) in fp32.  The
@@ -819,6 +891,10 @@ __global__ __launch_bounds__(256, FAST ? VISO_LK_MIN_WAVES_FAST : VISO_LK_MIN_WA
 // lk_point.  fp64 in both precision modes.
 constexpr double kWarpH = 4.0;  // the affine map's finite-difference step (anchor pixels)
 
+// ILLUM (viso_set_lk_illum): a per-patch gain and offset are
+// projected out of every level's alignment, and the level-0 pair is reported
+// and bounded.  Every line of that form sits behind `if constexpr (ILLUM)`.
+template <bool ILLUM>
 __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[4][2][kWinW * kWinH];
     const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -841,6 +917,8 @@ __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
     int shift = 0;
     double ub[2] = {0.0, 0.0}, ua[2] = {0.0, 0.0};
     double A00 = 0.0, A01 = 0.0, A10 = 0.0, A11 = 0.0;
+    // (ILLUM) the last accepted level-0 iteration's gain and offset
+    double gain = __builtin_nan(""), offset = __builtin_nan("");
     double uc, vc;
     project_px(cur_pose, K, P, 1.0, uc, vc);
     if (inside_px(uc, vc, w0, h0)) {  // current_frame->IsInside(Pw, 0)
@@ -923,7 +1001,57 @@ __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
 #pragma unroll
                     for (int q5 = 0; q5 < 5; ++q5)
                         in = in && 0 <= xs[q5] && xs[q5] + 1 < wr && 0 <= ys[q5] && ys[q5] + 1 < hr;
-                    if (__builtin_amdgcn_ballot_w64(in) == ~0ull) {
+                    if constexpr (ILLUM) {
+                        bool ran = false;
+                        if (__builtin_amdgcn_ballot_w64(in) == ~0ull) {
+                            LkIllumTemplate t;
+                            t.T = sample_px(ref, wr, hr, xs[0], ys[0]);
+                            const double J0 =
+                                -0.5 * (sample_px(ref, wr, hr, xs[1], ys[1]) - sample_px(ref, wr, hr, xs[2], ys[2]));
+                            const double J1 =
+                                -0.5 * (sample_px(ref, wr, hr, xs[3], ys[3]) - sample_px(ref, wr, hr, xs[4], ys[4]));
+                            // round 1: the means; round 2: the template's energy
+                            // and the Jacobian's components along Tc
+                            double sT, sJ0, sJ1;
+                            wave_tree_sum3(t.T, J0, J1, sT, sJ0, sJ1);
+                            t.m = sT * (1.0 / 64.0);
+                            t.Tc = t.T - t.m;
+                            double s0, s1;
+                            wave_tree_sum3(t.Tc * t.Tc, t.Tc * J0, t.Tc * J1, t.stt, s0, s1);
+                            // a flat template (or NaN) is skipped as a level
+                            // whose taps leave the reference level
+                            if (t.stt >= 64.0) {
+                                ran = true;
+                                // the two divisions on lanes 0 and 1
+                                const double cq = ((lane & 1) ? s1 : s0) / t.stt;
+                                const double c0 = readlane_f64(cq, 0), c1 = readlane_f64(cq, 1);
+                                t.P0 = (J0 - sJ0 * (1.0 / 64.0)) - c0 * t.Tc;
+                                t.P1 = (J1 - sJ1 * (1.0 / 64.0)) - c1 * t.Tc;
+                                double H00, H01, H11;
+                                wave_tree_sum3(t.P0 * t.P0, t.P0 * t.P1, t.P1 * t.P1, H00, H01, H11);
+                                const double H10 = H01;
+                                const double invdet = 1.0 / (H00 * H11 - H10 * H01);
+                                t.i00 = H11 * invdet;
+                                t.i10 = -H10 * invdet;
+                                t.i01 = -H01 * invdet;
+                                t.i11 = H00 * invdet;
+                                const LkIllumResult res =
+                                    lk_iterate_illum(t, w, h, level_ptr(cur, level), w, h, cu * s + px, cv * s + py,
+                                                     cu * s, cv * s, a.thresh, win);
+                                succ = res.succ;
+                                cu = cu + res.dx / s;
+                                cv = cv + res.dy / s;
+                                if (level == 0 && res.any) {
+                                    gain = 1.0 - res.ste / t.stt;
+                                    offset = (t.m - res.se * (1.0 / 64.0)) - gain * t.m;
+                                }
+                            }
+                        }
+                        if (!ran) {
+                            succ = false;
+                            skipped += 1;
+                        }
+                    } else if (__builtin_amdgcn_ballot_w64(in) == ~0ull) {
                         LkTemplate t;
                         t.I1 = sample_px(ref, wr, hr, xs[0], ys[0]);
                         t.J0 = -0.5 * (sample_px(ref, wr, hr, xs[1], ys[1]) - sample_px(ref, wr, hr, xs[2], ys[2]));
@@ -958,7 +1086,21 @@ __global__ __launch_bounds__(256, 4) void lk_warp_kernel(LkAlignArgs a) {
                 ua[0] = cu;
                 ua[1] = cv;
                 status = (uint8_t)(skipped << 4);
+                if constexpr (ILLUM) {
+                    // a flat or saturated current region matches any template
+                    // with gain 0 and cost 0: the gain is bounded (NaN fails)
+                    if (succ && !(1.0 / a.illum_max_gain <= gain && gain <= a.illum_max_gain)) {
+                        succ_out = 0;
+                        status = (uint8_t)((skipped << 4) | 3);
+                    }
+                }
             }
+        }
+    }
+    if constexpr (ILLUM) {
+        if (lane == 0 && a.illum_go) {
+            a.illum_go[2 * (o + i)] = gain;
+            a.illum_go[2 * (o + i) + 1] = offset;
         }
     }
     if (lane == 0) {
@@ -1331,7 +1473,10 @@ void launch_lk_align(const LkAlignArgs& a, hipStream_t stream) {
 void launch_lk_warp(const LkAlignArgs& a, hipStream_t stream) {
     if (a.n <= 0 || a.n_frames <= 0) return;
     const int gx = (((a.n + 3) / 4) + 7) / 8 * 8;  // multiple of 8: XCD-stable point groups
-    lk_warp_kernel<<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
+    if (a.illum)
+        lk_warp_kernel<true><<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
+    else
+        lk_warp_kernel<false><<<dim3(gx, a.n_frames), 256, 0, stream>>>(a);
 }
 
 // the background kernel's LDS request: static windows + dynamic = 84 KB, so

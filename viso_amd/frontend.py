@@ -428,6 +428,31 @@ class Viso(FrameHandler):
                       n.value, ctypes.byref(n))
         return A, shift, status
 
+    def set_lk_illum(self, mode: int, max_gain: float = 4.0) -> None:
+        """Illumination-invariant LK alignment (viso_set_lk_illum): a
+        per-patch gain and offset between the keyframe patch and the current
+        image are projected out of the warped alignment; an aligned point
+        whose gain is outside [1 / max_gain, max_gain] is failed (status 3).
+        Runs while set_lk_warp is on; kept, inert, otherwise.  mode 0 = off."""
+        _lib.call("viso_set_lk_illum", self.ctx.h, int(mode), float(max_gain))
+
+    def lk_illum(self) -> np.ndarray:
+        """viso_get_lk_illum: int64[8] = mode, frames aligned with it, then of
+        the last row: paired, aligned, status-3 points, 0, 0, 0."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_lk_illum", self.ctx.h, info.ctypes.data)
+        return info
+
+    def lk_illum_rows(self) -> np.ndarray:
+        """The last frame's (gain, offset) rows (viso_get_lk_illum_rows):
+        (n, 2), NaN where no level-0 iteration was accepted."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_lk_illum_rows", self.ctx.h, None, 0, ctypes.byref(n))
+        go = np.zeros((n.value, 2), np.float64)
+        if n.value:
+            _lib.call("viso_get_lk_illum_rows", self.ctx.h, go.ctypes.data, n.value, ctypes.byref(n))
+        return go
+
     def process_device(self, d_left: int, d_right: int | None, n: int, frame_stride: int):
         """Batched ingest of n frames resident in HBM (device pointers)."""
         _lib.call("viso_process_frames_device", self.ctx.h, d_left, d_right, n, frame_stride)
