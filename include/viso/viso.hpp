@@ -612,6 +612,27 @@ public:
         check(viso_get_reloc_seed_report(ctx_, r.report.data(), r.pose.data()), "viso_get_reloc_seed_report");
         return r;
     }
+    // Affine brightness per candidate in the relocalisation attempts
+    // (viso_set_reloc_illum; effective while SetRelocalise is on): every
+    // attempt of a lost frame estimates (pose, gain, offset) and rejects a
+    // gain outside [1 / max_gain, max_gain].  mode 0 = off.
+    void SetRelocIllum(int mode, double max_gain = 4.0) {
+        check(viso_set_reloc_illum(ctx_, mode, max_gain), "viso_set_reloc_illum");
+    }
+    // viso_get_reloc_illum's info[8]
+    std::array<int64_t, 8> GetRelocIllum() const {
+        std::array<int64_t, 8> info{};
+        check(viso_get_reloc_illum(ctx_, info.data()), "viso_get_reloc_illum");
+        return info;
+    }
+    // the last such attempt's (gain, offset) rows, 2 per candidate
+    std::vector<double> RelocIllumRows() const {
+        size_t n = 0;
+        check(viso_get_reloc_illum_rows(ctx_, nullptr, 0, &n), "viso_get_reloc_illum_rows");
+        std::vector<double> go(2 * n);
+        if (n) check(viso_get_reloc_illum_rows(ctx_, go.data(), n, &n), "viso_get_reloc_illum_rows");
+        return go;
+    }
     // one byte per pose: 0 tracked, 1 bad verdict, 2 lost, 3 recovered
     std::vector<uint8_t> GetFrameStatus() const {
         size_t n = 0;

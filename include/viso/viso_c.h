@@ -783,6 +783,49 @@ int viso_get_relocalise_report(viso_ctx* ctx, double* poses, double* report, siz
  * with the mode off.  The first min(cap, n) are written; *n = the poses. */
 int viso_get_frame_status(viso_ctx* ctx, uint8_t* status, size_t cap, size_t* n);
 
+/* The keyframe alignment with an affine brightness map per candidate (the
+ * repo's own spec, restated in tests/kf_align_illum_ref.py):
+ * viso_kf_align, with every candidate's state (T, g, o) in place of T — (seed,
+ * 1, 0) on level 3, each lower level from the state the level above kept.
+ * Points, good points, levels, passes, the order of the sums across points
+ * (list position p into accumulator p mod 16, the 16 added neighbours first)
+ * and the report are viso_kf_align's.  Per good point: R = the keyframe's
+ * sample, C = the current frame's, e = (g_j R + o_j) - C, and the 44 terms of
+ * viso_track_affine (below) with keyframe k's level as "last" and keyframe k's
+ * pose as L; d11 = 64 n_j.  The step is viso_track_affine's: (g, o) eliminated
+ * by the explicit 2x2 inverse, viso_kf_align's 6x6 solve on A' and b', then dg
+ * and do.  The decisions are viso_kf_align's with (T, g, o) for T: exits 1 and
+ * 5 restore pass j - 1's g and o too, and exit 3 is also taken when dg or do is
+ * not finite (a constant keyframe patch set: det = 0).  Status, from level 0's
+ * result, in this order: 2; 3; 5 not (1 / max_gain <= g <= max_gain) (max_gain
+ * finite, > 1: a foreign frame is otherwise explained by g -> 0); 4; 0.  The
+ * cost is the compensated residual at the current frame's scale, so it scales
+ * with g^2; max_cost keeps its meaning.  gain_offset: n_cand x 2, the kept g
+ * and o ((1, 0) when m < 6).  fp64 in both precision modes.  Every out-of-range
+ * or NULL argument returns VISO_ERR_ARG. */
+int viso_kf_align_illum(viso_ctx* ctx, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                        const uint8_t* cur_pyr, int32_t width, int32_t height, const double* points, int32_t n_points,
+                        const double* extra_seed12, int32_t n_extra, int32_t iterations, int32_t max_points,
+                        double max_cost, int32_t min_good_permille, double max_gain, double* poses_out, double* report,
+                        double* gain_offset, int32_t* winner);
+/* The form in the frame path.  mode 0 (default): off, max_gain is not read,
+ * nothing is launched or allocated.  mode 1: while viso_set_relocalise is on,
+ * every attempt of a lost frame (the first one and the one behind
+ * viso_set_reloc_seed's stage) runs as viso_kf_align_illum with this max_gain;
+ * the verdict, the bad run, the held pose, the pose-log and frame-log rows and
+ * viso_get_relocalise_report are unchanged.  With the relocalisation off the
+ * mode is kept, inert.  May be called while tracking (pending work is settled
+ * first). */
+int viso_set_reloc_illum(viso_ctx* ctx, int32_t mode, double max_gain);
+/* info = {mode, attempts run in this form, recoveries through it, the last
+ * such attempt's winner (-1: none), 0, 0, 0, 0}. */
+int viso_get_reloc_illum(viso_ctx* ctx, int64_t info[8]);
+/* The (g, o) rows of the last attempt run in this form, candidate by
+ * candidate: the first min(cap, n) are written (gain_offset2 may be NULL);
+ * *n = its candidates (0 before the first).  VISO_ERR_STATE while the mode is
+ * off. */
+int viso_get_reloc_illum_rows(viso_ctx* ctx, double* gain_offset2, size_t cap, size_t* n);
+
 /* Relocalisation seed (the repo's own spec, restated in
  * tests/reloc_seed_ref.py): a pose seed for viso_kf_align from
  * descriptor matches, independent of where tracking stopped.

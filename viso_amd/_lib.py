@@ -152,6 +152,11 @@ SIGNATURES = {
     "viso_get_relocalise": [_vp, _vp],
     "viso_get_relocalise_report": [_vp, _vp, _vp, _sz, _vp],
     "viso_get_frame_status": [_vp, _vp, _sz, _vp],
+    "viso_kf_align_illum": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _d, _i32, _d, _vp,
+                            _vp, _vp, _vp],
+    "viso_set_reloc_illum": [_vp, _i32, _d],
+    "viso_get_reloc_illum": [_vp, _vp],
+    "viso_get_reloc_illum_rows": [_vp, _vp, _sz, _vp],
     "viso_set_reloc_seed": [_vp, _i32, _i32, _i32, _d, _i32, ctypes.c_uint64],
     "viso_get_reloc_seed": [_vp, _vp],
     "viso_get_reloc_seed_report": [_vp, _vp, _vp],

@@ -495,6 +495,53 @@ class Context:
                   ctypes.byref(winner))
         return {"poses": poses, "report": report, "winner": int(winner.value)}
 
+    def kf_align_illum(self, kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None, iterations: int = 10,
+                       max_points: int = 512, max_cost: float = 57600.0, min_good_permille: int = 500,
+                       max_gain: float = 4.0):
+        """viso_kf_align_illum: ``kf_align`` with an affine brightness map
+        (g, o) estimated per candidate (viso_set_reloc_illum; DESIGN.md §25);
+        status 5 rejects a gain outside [1 / max_gain, max_gain].  Returns
+        dict(poses (n_cand, 12), report (n_cand, 20), gain_offset (n_cand, 2),
+        winner)."""
+        kfp = np.ascontiguousarray(np.stack(kf_pyrs) if isinstance(kf_pyrs, (list, tuple)) else kf_pyrs,
+                                   dtype=np.uint8)
+        kposes = np.ascontiguousarray(kf_poses, dtype=np.float64).reshape(-1, 12)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        seed = None if extra_seed is None else np.ascontiguousarray(extra_seed, dtype=np.float64).reshape(12)
+        n_kf = kposes.shape[0]
+        n_cand = n_kf * (1 if seed is None else 2)
+        poses = np.zeros((n_cand, 12), np.float64)
+        report = np.zeros((n_cand, 20), np.float64)
+        gain_offset = np.zeros((n_cand, 2), np.float64)
+        winner = ctypes.c_int32(-1)
+        _lib.call("viso_kf_align_illum", self.h, _p(kfp), _p(kposes), n_kf,
+                  _p(np.ascontiguousarray(cur_pyr, dtype=np.uint8)), width, height, _p(pts), pts.shape[0], _p(seed),
+                  0 if seed is None else 1, int(iterations), int(max_points), float(max_cost), int(min_good_permille),
+                  float(max_gain), _p(poses), _p(report), _p(gain_offset), ctypes.byref(winner))
+        return {"poses": poses, "report": report, "gain_offset": gain_offset, "winner": int(winner.value)}
+
+    def set_reloc_illum(self, mode: int, max_gain: float = 4.0) -> None:
+        """viso_set_reloc_illum: while the relocalisation is
+        on, every attempt of a lost frame estimates (T, g, o); 0 = off."""
+        _lib.call("viso_set_reloc_illum", self.h, int(mode), float(max_gain))
+
+    def get_reloc_illum(self) -> np.ndarray:
+        """viso_get_reloc_illum: int64[8] = mode, attempts run in this form,
+        recoveries through it, the last such attempt's winner (-1), 0, 0, 0, 0."""
+        info = np.zeros(8, np.int64)
+        _lib.call("viso_get_reloc_illum", self.h, _p(info))
+        return info
+
+    def reloc_illum_rows(self) -> np.ndarray:
+        """viso_get_reloc_illum_rows: the (g, o) rows (n_cand, 2) of the last
+        attempt run in this form."""
+        n = ctypes.c_size_t(0)
+        _lib.call("viso_get_reloc_illum_rows", self.h, None, 0, ctypes.byref(n))
+        rows = np.zeros((max(int(n.value), 1), 2))
+        if n.value:
+            _lib.call("viso_get_reloc_illum_rows", self.h, _p(rows), n.value, ctypes.byref(n))
+        return rows[:n.value]
+
     def track_affine(self, last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations: int = 10):
         """viso_track_affine: the brightness-compensated tracking stage
         (viso_set_brightness) on host data with the context's
@@ -707,6 +754,14 @@ def kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None,
     return default_context(width, height, device, K).kf_align(kf_pyrs, kf_poses, cur_pyr, width, height, points,
                                                               extra_seed, iterations, max_points, max_cost,
                                                               min_good_permille)
+
+
+def kf_align_illum(kf_pyrs, kf_poses, cur_pyr, width, height, points, extra_seed=None, iterations=10, max_points=512,
+                   max_cost=57600.0, min_good_permille=500, max_gain=4.0, K=None, device: int = 0):
+    """``Context.kf_align_illum`` on the cached context of intrinsics K."""
+    return default_context(width, height, device, K).kf_align_illum(kf_pyrs, kf_poses, cur_pyr, width, height, points,
+                                                                    extra_seed, iterations, max_points, max_cost,
+                                                                    min_good_permille, max_gain)
 
 
 def track_affine(last_pyr, cur_pyr, width, height, points, pose_last, seed, iterations=10, K=None, device: int = 0):

@@ -515,6 +515,16 @@ struct viso_ctx {
     int reloc_attempt(int cur, int li, bool* won, int only_kf = -1, const double* seed = nullptr);
     // a lost frame: the attempt, its status, a winner's LK alignment
     int reloc_lost_frame(int cur, int li);
+    // the illumination form of the attempt (viso_set_reloc_illum; reloc.hip
+    // kf_align_kernel<true>): while on, every reloc_attempt
+    // estimates (T, g, o) per candidate.  0 = off (reloc_illum_buf null until
+    // the mode is first set on).  reloc_illum_buf: the last such attempt's
+    // (g, o) rows, 16 x 2 doubles
+    int reloc_illum_mode = 0;
+    double reloc_illum_max_gain = 0.0;
+    int64_t reloc_illum_attempts = 0, reloc_illum_recoveries = 0;
+    int reloc_illum_last_winner = -1, reloc_illum_last_cands = 0;
+    viso::DevBuf reloc_illum_buf;
 
     // relocalisation seed (viso_set_reloc_seed; relocseed.hip):
     // a lost frame whose attempt has no winner runs the seed stage from the

@@ -228,7 +228,7 @@ void viso_ctx::release() {
                       &lk_tmpl_kf, &lk_tmpl_uv, &pose_log, &frame_log, &hbg_buf, &mono_buf, &mapwin_buf, &refine_rep,
                       &pt_tracks, &cull_buf, &prefine_buf, &warp_buf, &seed_buf, &reloc_buf, &rseed_buf, &rect_map[0],
                       &rect_map[1], &rect_raw[0], &rect_raw[1], &rect_right, &bright_buf, &robust_buf,
-                      &illum_buf};
+                      &illum_buf, &reloc_illum_buf};
     for (DevBuf* b : bufs) b->release();
     if (h_ctl) (void)hipHostFree(h_ctl);
     if (h_int) (void)hipHostFree(h_int);
@@ -1071,6 +1071,7 @@ int viso_ctx::reloc_lost_frame(int cur, int li) {
     set_frame_status(li, won ? 3 : 2);
     if (!won) return VISO_OK;
     ++reloc_recoveries;
+    if (reloc_illum_mode) ++reloc_illum_recoveries;
     reloc_lost = false;
     reloc_bad_run = 0;
     hold(cur);

@@ -446,8 +446,13 @@ struct KfAlignArgs {
     double* log_host;
     double* flog;
     int log_index;
+    // the illumination form: gain_offset non-null selects it;
+    // the kept (g, o) of every candidate, n_cand x 2
+    double max_gain;
+    double* gain_offset;
 };
-// two launches: the candidates (one workgroup each), then the choice
+// two launches: the candidates (one workgroup each; kf_align_kernel<true> when
+// a.gain_offset is set), then the choice
 void launch_kf_align(const KfAlignArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- relocalisation seed

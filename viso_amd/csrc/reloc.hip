@@ -24,6 +24,13 @@
 // round through LDS.  A second launch of one wave picks the winner.  No
 // atomics, no inline assembly; fp64 in both precision modes,
 // -ffp-contract=off.
+//
+// The illumination form (viso_kf_align_illum, viso_set_reloc_illum; DESIGN.md
+// §25, restated in tests/kf_align_illum_ref.py) is kf_align_kernel<true>: the
+// state of a candidate is (T, g, o), the error (g R + o) - C, a point has the
+// brightness chain's 44 terms (five wave trees, lane t < 44 forms term t), wave
+// 0 eliminates (g, o) ahead of the same 6x6 solve, and a gain outside
+// [1 / max_gain, max_gain] is status 5.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -38,28 +45,35 @@ namespace {
 
 constexpr int kAlWaves = 16;
 constexpr int kAlLanes = 64 * kAlWaves;
-constexpr int kAlTerms = 28;  // H upper triangle (21, row-major), b (6), cost
+constexpr int kAlTerms = 28;       // H upper triangle (21, row-major), b (6), cost
+constexpr int kAlIllumTerms = 44;  // the illumination form (§25): then B (12), d00, d01, c0, c1
 constexpr int kAlMaxPoints = 1024;
 constexpr double kAlDeltaThresh = 0.005;  // the reference's delta_thresh
 
+// kIllum (viso_kf_align_illum): 44 terms, and the state carries
+// g and o behind the pose (T[12], T[13])
+template <bool kIllum>
 struct AlignLds {
+    static constexpr int kTerms = kIllum ? kAlIllumTerms : kAlTerms;
+    static constexpr int kState = kIllum ? 14 : 12;
     int table[kAlWaves];
     unsigned short idx[kAlMaxPoints];  // the map index of list position p
-    double acc[kAlWaves][kAlTerms];
+    double acc[kAlWaves][kTerms];
     int cnt[kAlWaves];
-    double S[kAlTerms];
+    double S[kTerms];
     int n;
-    double T[12];
+    double T[kState];
     int done;
     // wave 0's: pass j - 1, and the level's result
-    double prevT[12], prev_cost;
+    double prevT[kState], prev_cost;
     int prev_n;
     int res_exit, res_n;
     double res_cost;
 };
 
 // neighbours first over the 16 accumulators of one sum
-__device__ inline double tree16(const double (*acc)[kAlTerms], int s) {
+template <int kTerms>
+__device__ inline double tree16(const double (*acc)[kTerms], int s) {
     double v[kAlWaves];
 #pragma unroll
     for (int w = 0; w < kAlWaves; ++w) v[w] = acc[w][s];
@@ -92,9 +106,12 @@ __device__ inline double project_level(const double* pose, const double* K, cons
 // The decisions of pass j and the step, on wave 0 behind the pass's sums in
 // L.S / L.n: either the level's result (L.T, the report's level row, L.done) or
 // T_{j+1} in L.T.  Every lane computes the same values; lane c < 6 solves
-// column c of the inverse; lane 0 stores.
-__device__ __attribute__((always_inline)) inline void align_decide(AlignLds& L, int j, int iterations, double* row,
-                                                                   int lane) {
+// column c of the inverse; lane 0 stores.  kIllum: (g, o) are eliminated from
+// the 44 sums first (bright_decide's Schur complement, d11 = 64 n), the 6x6
+// solve runs on A' and b', and g, o and pass j - 1's copies move with the pose.
+template <bool kIllum>
+__device__ __attribute__((always_inline)) inline void align_decide(AlignLds<kIllum>& L, int j, int iterations,
+                                                                   double* row, int lane) {
     const int n = L.n;
     const double cost = L.S[27] / (double)n;
     int ex = -1;
@@ -114,17 +131,45 @@ __device__ __attribute__((always_inline)) inline void align_decide(AlignLds& L, 
 #pragma unroll
     for (int q = 0; q < 12; ++q) T[q] = L.T[q];
     double xi[6];
+    double dg = 0.0, dof = 0.0;
     if (ex < 0) {
         // ---- inverse6 (Eigen PartialPivLU: first maximal |pivot| wins)
         double A[36];
         int tr[6];
+        double Y0[6], Y1[6], bp[6], q0 = 0.0, q1 = 0.0;
+        if constexpr (kIllum) {
+            // (g, o) eliminated: A' = A - B D^-1 B^T, b' = b - B D^-1 c
+            const double* S = L.S;
+            const double d00 = S[40], d01 = S[41], c0 = S[42], c1 = S[43];
+            const double d11 = 64.0 * (double)n;
+            const double det = d00 * d11 - d01 * d01;
+            q0 = (d11 * c0 - d01 * c1) / det;
+            q1 = (d00 * c1 - d01 * c0) / det;
 #pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                const int r1 = r < c ? r : c, c1 = r < c ? c : r;
-                A[6 * r + c] = L.S[r1 * 6 - (r1 * (r1 - 1)) / 2 + (c1 - r1)];
+            for (int e = 0; e < 6; ++e) {
+                Y0[e] = (d11 * S[28 + e] - d01 * S[34 + e]) / det;
+                Y1[e] = (d00 * S[34 + e] - d01 * S[28 + e]) / det;
             }
+            int k = 0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = r; c < 6; ++c, ++k) {
+                    const double v = S[k] - (S[28 + r] * Y0[c] + S[34 + r] * Y1[c]);
+                    A[6 * r + c] = v;
+                    A[6 * c + r] = v;
+                }
+#pragma unroll
+            for (int e = 0; e < 6; ++e) bp[e] = S[21 + e] - (S[28 + e] * q0 + S[34 + e] * q1);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    const int r1 = r < c ? r : c, c1 = r < c ? c : r;
+                    A[6 * r + c] = L.S[r1 * 6 - (r1 * (r1 - 1)) / 2 + (c1 - r1)];
+                }
+        }
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             int p = k;
@@ -185,11 +230,29 @@ __device__ __attribute__((always_inline)) inline void align_decide(AlignLds& L, 
         bool finite = true;
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
-            double v = readlane_f64(x[r], 0) * L.S[21];
+            double v;
+            if constexpr (kIllum) {
+                v = readlane_f64(x[r], 0) * bp[0];
 #pragma unroll
-            for (int c = 1; c < 6; ++c) v = v + readlane_f64(x[r], c) * L.S[21 + c];
+                for (int c = 1; c < 6; ++c) v = v + readlane_f64(x[r], c) * bp[c];
+            } else {
+                v = readlane_f64(x[r], 0) * L.S[21];
+#pragma unroll
+                for (int c = 1; c < 6; ++c) v = v + readlane_f64(x[r], c) * L.S[21 + c];
+            }
             xi[r] = v;
             finite = finite && finite_f64(v);
+        }
+        if constexpr (kIllum) {
+            double s0 = Y0[0] * xi[0], s1 = Y1[0] * xi[0];
+#pragma unroll
+            for (int e = 1; e < 6; ++e) {
+                s0 = s0 + Y0[e] * xi[e];
+                s1 = s1 + Y1[e] * xi[e];
+            }
+            dg = q0 - s0;
+            dof = q1 - s1;
+            finite = finite && finite_f64(dg) && finite_f64(dof);
         }
         if (!finite) ex = 3;
     }
@@ -199,7 +262,7 @@ __device__ __attribute__((always_inline)) inline void align_decide(AlignLds& L, 
             const double r_cost = ex == 4 ? std::numeric_limits<double>::quiet_NaN() : use_prev ? L.prev_cost : cost;
             if (use_prev)
 #pragma unroll
-                for (int q = 0; q < 12; ++q) L.T[q] = L.prevT[q];
+                for (int q = 0; q < AlignLds<kIllum>::kState; ++q) L.T[q] = L.prevT[q];
             row[0] = (double)ex;
             row[1] = (double)(use_prev ? j - 1 : ex == 4 ? 0 : j);
             row[2] = (double)r_n;
@@ -225,14 +288,26 @@ __device__ __attribute__((always_inline)) inline void align_decide(AlignLds& L, 
                 L.prevT[q] = T[q];
                 L.T[q] = nT[q];
             }
+            if constexpr (kIllum) {
+                const double g = L.T[12], o = L.T[13];
+                L.prevT[12] = g;
+                L.prevT[13] = o;
+                L.T[12] = g + dg;
+                L.T[13] = o + dof;
+            }
             L.prev_cost = cost;
             L.prev_n = n;
         }
     }
 }
 
+// kIllum: the candidate's state is (T, g, o), the error is
+// (g R + o) - C, a point has bright_pass_kernel's 44 terms (five wave trees,
+// lane t < 44 forms term t); status 5 and the gain_offset row at the end.
+template <bool kIllum>
 __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
-    __shared__ AlignLds L;
+    constexpr int kTerms = AlignLds<kIllum>::kTerms;
+    __shared__ AlignLds<kIllum> L;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int cand = blockIdx.x;
     const int per_kf = 1 + a.n_extra;
@@ -245,6 +320,8 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
     for (int q = 0; q < 12; ++q) kfp[q] = a.kf_poses[12 * (size_t)k + q];
     const double* seed = s ? a.extra_seed : a.kf_poses + 12 * (size_t)k;
     if (tid < 12) L.T[tid] = seed[tid];
+    if constexpr (kIllum)
+        if (tid == 12 || tid == 13) L.T[tid] = tid == 12 ? 1.0 : 0.0;  // (g, o) = (1, 0)
     if (tid == 0) L.done = 0;  // the levels finished
 
     // ---- step 1: the first max_points map points keyframe k sees, in map order
@@ -279,6 +356,10 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
                 rep[6 + 4 * q] = 0.0;
                 rep[7 + 4 * q] = qnan;
             }
+            if constexpr (kIllum) {
+                a.gain_offset[2 * (size_t)cand] = 1.0;
+                a.gain_offset[2 * (size_t)cand + 1] = 0.0;
+            }
         }
         if (tid < 12) pose_out[tid] = seed[tid];
         return;
@@ -298,6 +379,10 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
                     tb = q;
                 }
         if (lane >= 21 && lane < 27) ta = lane - 21;
+        if constexpr (kIllum) {  // entry ta of B's columns for 28 <= t < 40
+            if (lane >= 28 && lane < 34) ta = lane - 28;
+            if (lane >= 34 && lane < 40) ta = lane - 34;
+        }
     }
     const double px = (double)((lane >> 3) - kHalfPatch), py = (double)((lane & 7) - kHalfPatch);
     const double hp = 4.0;
@@ -313,6 +398,11 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
             double T[12];
 #pragma unroll
             for (int e = 0; e < 12; ++e) T[e] = L.T[e];
+            double gain = 1.0, offs = 0.0;
+            if constexpr (kIllum) {
+                gain = L.T[12];
+                offs = L.T[13];
+            }
             double acc = 0.0;
             int cnt = 0;
             for (int p = wave; p < m; p += kAlWaves) {
@@ -344,7 +434,10 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
                 J1[5] = fys * x / z;
                 // the lane's pixel
                 const double xc = uc + px, yc = vc + py;
-                const double err = sample_px(kimg, w, h, ur + px, vr + py) - sample_px(cimg, w, h, xc, yc);
+                const double R = sample_px(kimg, w, h, ur + px, vr + py);
+                const double C = sample_px(cimg, w, h, xc, yc);
+                double err = R - C;
+                if constexpr (kIllum) err = (gain * R + offs) - C;
                 double g0, g1;
                 gradient_px(cimg, w, h, xc, yc, g0, g1);
                 double G[6];
@@ -353,14 +446,30 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
                 const double J0a = pick6(J0, ta), J0b = pick6(J0, tb), J1a = pick6(J1, ta), J1b = pick6(J1, tb);
                 const double th = (G[0] * (J0a * J0b) + G[1] * (J0a * J1b + J1a * J0b)) + G[2] * (J1a * J1b);
                 const double tbv = G[3] * J0a + G[4] * J1a;
-                const double term = lane < 21 ? th : lane < 27 ? tbv : G[5];
+                double term = lane < 21 ? th : lane < 27 ? tbv : G[5];
+                if constexpr (kIllum) {
+                    // the nine sums of B, D and c, as bright_pass_kernel forms them
+                    double B[9];
+                    wave_tree_sum3_desc(g0 * R, g1 * R, g0, B[0], B[1], B[2]);
+                    wave_tree_sum3_desc(g1, R * R, R, B[3], B[4], B[5]);
+                    wave_tree_sum3_desc(err * R, err, 0.0, B[6], B[7], B[8]);
+                    const double tB0 = -(B[0] * J0a + B[1] * J1a);
+                    const double tB1 = -(B[2] * J0a + B[3] * J1a);
+                    term = lane < 28    ? term
+                           : lane < 34  ? tB0
+                           : lane < 40  ? tB1
+                           : lane == 40 ? B[4]
+                           : lane == 41 ? B[5]
+                           : lane == 42 ? -B[6]
+                                        : -B[7];
+                }
                 acc = acc + term;
                 cnt += 1;
             }
-            if (lane < kAlTerms) L.acc[wave][lane] = acc;
+            if (lane < kTerms) L.acc[wave][lane] = acc;
             if (lane == 0) L.cnt[wave] = cnt;
             __syncthreads();
-            if (tid < kAlTerms) L.S[tid] = tree16(L.acc, tid);
+            if (tid < kTerms) L.S[tid] = tree16(L.acc, tid);
             if (tid == 64) {
                 int c = 0;
                 for (int v = 0; v < kAlWaves; ++v) c += L.cnt[v];
@@ -377,8 +486,15 @@ __global__ __launch_bounds__(kAlLanes) void kf_align_kernel(KfAlignArgs a) {
         const int ex = L.res_exit, n = L.res_n;
         const double cost = L.res_cost;
         int status = 0;
+        bool gain_ok = true;  // (the negated form rejects a NaN too)
+        if constexpr (kIllum) {
+            gain_ok = 1.0 / a.max_gain <= L.T[12] && L.T[12] <= a.max_gain;
+            a.gain_offset[2 * (size_t)cand] = L.T[12];
+            a.gain_offset[2 * (size_t)cand + 1] = L.T[13];
+        }
         if (ex == 4) status = 2;
         else if (n * 1000 < a.min_good_permille * m) status = 3;
+        else if (!gain_ok) status = 5;
         else if (!(cost <= a.max_cost)) status = 4;
         rep[0] = (double)status;
         rep[1] = (double)m;
@@ -431,7 +547,8 @@ __global__ __launch_bounds__(64) void kf_align_pick_kernel(KfAlignArgs a, int n_
 
 void launch_kf_align(const KfAlignArgs& a, hipStream_t stream) {
     const int n_cand = a.n_kf * (1 + a.n_extra);
-    kf_align_kernel<<<n_cand, kAlLanes, 0, stream>>>(a);
+    if (a.gain_offset) kf_align_kernel<true><<<n_cand, kAlLanes, 0, stream>>>(a);
+    else kf_align_kernel<false><<<n_cand, kAlLanes, 0, stream>>>(a);
     kf_align_pick_kernel<<<1, 64, 0, stream>>>(a, n_cand);
 }
 
@@ -509,6 +626,11 @@ int viso_ctx::reloc_attempt(int cur, int li, bool* won, int only_kf, const doubl
     a.log_host = log_host(li);
     a.flog = flog();
     a.log_index = li;
+    const bool illum = reloc_illum_mode != 0;  // viso_set_reloc_illum: every attempt in the (T, g, o) form
+    if (illum) {
+        a.max_gain = reloc_illum_max_gain;
+        a.gain_offset = (double*)reloc_illum_buf.ptr;
+    }
     {
         TimedRegion t(timing, VISO_KERNEL_RELOC, stream);
         launch_kf_align(a, stream);
@@ -520,21 +642,31 @@ int viso_ctx::reloc_attempt(int cur, int li, bool* won, int only_kf, const doubl
     reloc_last_frame = frames;
     reloc_last_winner = h_int[40];
     reloc_last_cands = 2 * n_kf;
+    if (illum) {
+        ++reloc_illum_attempts;
+        reloc_illum_last_winner = reloc_last_winner;
+        reloc_illum_last_cands = reloc_last_cands;
+    }
     *won = reloc_last_winner >= 0;
     return VISO_OK;
 }
 
-extern "C" {
+namespace {
 
-int viso_kf_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf, const uint8_t* cur_pyr,
+bool gain_bound_ok(double max_gain) { return std::isfinite(max_gain) && max_gain > 1.0; }
+
+// viso_kf_align, and viso_kf_align_illum (illum: max_gain and gain_offset are
+// its two arguments): one attempt on host data through the frame path's launches.
+int kf_align_host(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf, const uint8_t* cur_pyr,
                   int32_t width, int32_t height, const double* points, int32_t n, const double* extra_seed12,
                   int32_t n_extra, int32_t iterations, int32_t max_points, double max_cost, int32_t min_good_permille,
-                  double* poses_out, double* report, int32_t* winner) {
+                  bool illum, double max_gain, double* poses_out, double* report, double* gain_offset,
+                  int32_t* winner) {
     if (!c || !kf_pyrs || !kf_poses || n_kf < 1 || n_kf > kMaxKeyframes || !cur_pyr || width < 64 || height < 64 ||
         width > kMaxWidth || height > kMaxWidth || n < 0 || n > kMaxMapPoints || (n > 0 && !points) || n_extra < 0 ||
         n_extra > 1 || (n_extra == 1 && !extra_seed12) || !align_params_ok(iterations, max_points, max_cost,
                                                                            min_good_permille) ||
-        !poses_out || !report || !winner)
+        !poses_out || !report || !winner || (illum && (!gain_bound_ok(max_gain) || !gain_offset)))
         return VISO_ERR_ARG;
     if (int rc = c->settle()) return rc;  // (host-frame work left pending)
     VISO_HIP_CHECK(hipSetDevice(c->device));
@@ -543,7 +675,8 @@ int viso_kf_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, i
     Bump b;
     const size_t o_kf = b.take(g.bytes * (size_t)n_kf), o_kp = b.take(96 * (size_t)n_kf), o_c = b.take(g.bytes),
                  o_p = b.take(24 * (size_t)std::max(n, 1)), o_s = b.take(96), o_po = b.take(96 * (size_t)n_cand),
-                 o_r = b.take(8 * (size_t)kAlignReport * n_cand), o_w = b.take(4);
+                 o_r = b.take(8 * (size_t)kAlignReport * n_cand), o_w = b.take(4),
+                 o_go = b.take(illum ? 16 * (size_t)n_cand : 0);
     if (int rc = c->scratch_a.ensure(b.off)) return rc;
     char* base = (char*)c->scratch_a.ptr;
     VISO_HIP_CHECK(hipMemcpyAsync(base + o_kf, kf_pyrs, g.bytes * (size_t)n_kf, hipMemcpyHostToDevice, c->stream));
@@ -573,6 +706,10 @@ int viso_kf_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, i
     a.report = (double*)(base + o_r);
     a.winner = (int*)(base + o_w);
     a.log_index = -1;
+    if (illum) {
+        a.max_gain = max_gain;
+        a.gain_offset = (double*)(base + o_go);
+    }
     {
         TimedRegion t(c->timing, VISO_KERNEL_RELOC, c->stream);
         launch_kf_align(a, c->stream);
@@ -581,9 +718,77 @@ int viso_kf_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, i
     VISO_HIP_CHECK(hipMemcpyAsync(poses_out, a.poses_out, 96 * (size_t)n_cand, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(report, a.report, 8 * (size_t)kAlignReport * n_cand, hipMemcpyDeviceToHost,
                                   c->stream));
+    if (illum)
+        VISO_HIP_CHECK(hipMemcpyAsync(gain_offset, a.gain_offset, 16 * (size_t)n_cand, hipMemcpyDeviceToHost,
+                                      c->stream));
     VISO_HIP_CHECK(hipMemcpyAsync(c->h_int + 40, a.winner, 4, hipMemcpyDeviceToHost, c->stream));
     VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
     *winner = c->h_int[40];
+    return VISO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int viso_kf_align(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf, const uint8_t* cur_pyr,
+                  int32_t width, int32_t height, const double* points, int32_t n, const double* extra_seed12,
+                  int32_t n_extra, int32_t iterations, int32_t max_points, double max_cost, int32_t min_good_permille,
+                  double* poses_out, double* report, int32_t* winner) {
+    return kf_align_host(c, kf_pyrs, kf_poses, n_kf, cur_pyr, width, height, points, n, extra_seed12, n_extra,
+                         iterations, max_points, max_cost, min_good_permille, false, 0.0, poses_out, report, nullptr,
+                         winner);
+}
+
+int viso_kf_align_illum(viso_ctx* c, const uint8_t* kf_pyrs, const double* kf_poses, int32_t n_kf,
+                        const uint8_t* cur_pyr, int32_t width, int32_t height, const double* points, int32_t n,
+                        const double* extra_seed12, int32_t n_extra, int32_t iterations, int32_t max_points,
+                        double max_cost, int32_t min_good_permille, double max_gain, double* poses_out, double* report,
+                        double* gain_offset, int32_t* winner) {
+    return kf_align_host(c, kf_pyrs, kf_poses, n_kf, cur_pyr, width, height, points, n, extra_seed12, n_extra,
+                         iterations, max_points, max_cost, min_good_permille, true, max_gain, poses_out, report,
+                         gain_offset, winner);
+}
+
+// The illumination form in the frame path.  Takes effect while
+// viso_set_relocalise is on; off, nothing is allocated for it.
+int viso_set_reloc_illum(viso_ctx* c, int32_t mode, double max_gain) {
+    if (!c || (mode != 0 && mode != 1) || (mode == 1 && !gain_bound_ok(max_gain))) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    if (mode == 1) {
+        VISO_HIP_CHECK(hipSetDevice(c->device));
+        if (!c->reloc_illum_buf.ptr) {
+            const size_t bytes = 16 * (size_t)kMaxAlignCands;
+            if (int rc = c->reloc_illum_buf.ensure(bytes)) return rc;
+            VISO_HIP_CHECK(hipMemsetAsync(c->reloc_illum_buf.ptr, 0xff, bytes, c->stream));  // NaN until written
+        }
+        c->reloc_illum_max_gain = max_gain;
+    }
+    c->reloc_illum_mode = mode;
+    return VISO_OK;
+}
+
+int viso_get_reloc_illum(viso_ctx* c, int64_t info[8]) {
+    if (!c || !info) return VISO_ERR_ARG;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    info[0] = c->reloc_illum_mode;
+    info[1] = c->reloc_illum_attempts;
+    info[2] = c->reloc_illum_recoveries;
+    info[3] = c->reloc_illum_last_winner;
+    return VISO_OK;
+}
+
+int viso_get_reloc_illum_rows(viso_ctx* c, double* gain_offset2, size_t cap, size_t* n) {
+    if (!c) return VISO_ERR_ARG;
+    if (!c->reloc_illum_mode) return VISO_ERR_STATE;
+    if (int rc = c->settle()) return rc;  // (host-frame work left pending)
+    const size_t total = (size_t)c->reloc_illum_last_cands, m = std::min(cap, total);
+    if (n) *n = total;
+    if (m == 0 || !gain_offset2) return VISO_OK;
+    VISO_HIP_CHECK(hipSetDevice(c->device));
+    VISO_HIP_CHECK(hipMemcpyAsync(gain_offset2, c->reloc_illum_buf.ptr, 16 * m, hipMemcpyDeviceToHost, c->stream));
+    VISO_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VISO_OK;
 }
 

@@ -316,6 +316,22 @@ class Viso(FrameHandler):
         """The last seed stage's (report (12,), pose (12,))."""
         return self.ctx.reloc_seed_report()
 
+    def set_reloc_illum(self, mode: int, max_gain: float = 4.0) -> None:
+        """Affine brightness per candidate in the relocalisation attempts
+        (viso_set_reloc_illum; takes effect while set_relocalise is on): every
+        attempt of a lost frame estimates (pose, gain, offset) and rejects a
+        gain outside [1 / max_gain, max_gain].  0 = off."""
+        self.ctx.set_reloc_illum(mode, max_gain)
+
+    def reloc_illum(self) -> np.ndarray:
+        """viso_get_reloc_illum: int64[8] = mode, attempts run in this form,
+        recoveries through it, the last such attempt's winner (-1), 0, 0, 0, 0."""
+        return self.ctx.get_reloc_illum()
+
+    def reloc_illum_rows(self) -> np.ndarray:
+        """The last such attempt's (gain, offset) rows (n_cand, 2)."""
+        return self.ctx.reloc_illum_rows()
+
     def set_brightness(self, iterations: int = 10) -> None:
         """Brightness-compensated tracking (viso_set_brightness): every
         tracking frame's pose is estimated together with an affine brightness
