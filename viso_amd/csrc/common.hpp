@@ -281,48 +281,29 @@ __device__ inline double swizzle_xor16_f64(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// The same tree over 64 leaves whose first level (leaf 2 p + leaf 2 p + 1) is
-// already formed: lane p < 32 holds in a[k] the pair p's sum of value k, lane
-// 32 + p its sum of value 14 + k (what the first level below keeps in lanes
-// 2 p and 2 p + 1).  The remaining levels pair p with p ^ 1, ^ 2, ^ 4, ^ 8,
-// ^ 16 -- leaves ^ 2 .. ^ 32, the ascending-xor order -- and every partial sum
-// is the one reduce_scatter_28 forms.  On return lane l (and l ^ 16) holds
-// value index 14*b5 + 7*b0 + 4*b1 + 2*b2 + b3 when 4*b1 + 2*b2 + b3 < 7.
-__device__ inline double reduce_scatter_28_paired(const double* a, int* value_index) {
-    const int lane = threadIdx.x & 63;
-    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8, b5 = lane & 32;
-    double c[7];
+// The same tree over 64 leaves with four levels formed in registers: lane
+// l < 56 is (g = l & 3, s = l >> 2) and holds in x[j] leaf 16 g + j of value
+// 2 s (.x) and of value 2 s + 1 (.y), an absent leaf as +0.0.  The 16 leaves
+// of a value are an index-aligned subtree of the ascending-xor tree, so
+// ((x0 + x1) + (x2 + x3)) + ... in one lane is the tree's first four levels
+// with the same pairing, 15 plain adds per value.  The remaining levels are
+// leaves ^ 16 and ^ 32, i.e. g ^ 1 and g ^ 2: xor 1 as a reduce-scatter step
+// (even g keeps value 2 s, odd g value 2 s + 1) and xor 2 as a butterfly,
+// both by DPP quad_perm.  On return lane l < 56 holds value 2 s + (g & 1)
+// (lane l ^ 2 a copy).  Lanes 56..63 pass zeros.  Requires EXEC = all lanes.
+__device__ inline double reduce_tree16_pairs(double2* x) {
+    const bool b0 = threadIdx.x & 1;
 #pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const double send = dsel(b0, a[k], a[7 + k]);
-        const double keep = dsel(b0, a[7 + k], a[k]);
-        c[k] = keep + dpp_f64<0xB1>(send);
-    }
-    double d[4];
+    for (int st = 1; st < 16; st <<= 1)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double hi = k < 3 ? c[4 + k] : 0.0;
-        const double send = dsel(b1, c[k], hi);
-        const double keep = dsel(b1, hi, c[k]);
-        d[k] = keep + dpp_f64<0x4E>(send);
-    }
-    double e[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double send = dsel(b2, d[k], d[2 + k]);
-        const double keep = dsel(b2, d[2 + k], d[k]);
-        const double recv = dsel(b2, dpp_f64<0x114>(send), dpp_f64<0x104>(send));  // row_shr:4 / row_shl:4
-        e[k] = keep + recv;
-    }
-    const double send = dsel(b3, e[0], e[1]);
-    const double keep = dsel(b3, e[1], e[0]);
-    double f = keep + dpp_f64<0x128>(send);  // row_ror:8 = the xor-8 partner
-    double ra, rb;
-    permlane16_swap_f64(f, f, ra, rb);  // xor 16: row pairs (0,1), (2,3)
-    f = ra + rb;
-    const int local = (b1 ? 4 : 0) + (b2 ? 2 : 0) + (b3 ? 1 : 0);
-    *value_index = local >= 7 ? -1 : (b5 ? 14 : 0) + (b0 ? 7 : 0) + local;
-    return f;
+        for (int j = 0; j < 16; j += 2 * st) {
+            x[j].x = x[j].x + x[j + st].x;
+            x[j].y = x[j].y + x[j + st].y;
+        }
+    const double send = dsel(b0, x[0].x, x[0].y);
+    const double keep = dsel(b0, x[0].y, x[0].x);
+    const double c = keep + dpp_f64<0xB1>(send);  // quad_perm [1,0,3,2]: g ^ 1
+    return c + dpp_f64<0x4E>(c);                  // quad_perm [2,3,0,1]: g ^ 2
 }
 
 __device__ inline double reduce_scatter_28(const double* v, int* value_index) {

@@ -22,14 +22,21 @@
 //     reduce-scatter (the canonical wave tree, common.hpp).  A workgroup owns
 //     a tile of T = map_tile(n, 256) = min(64, ceil(n / 256)) consecutive
 //     points (247 tiles of 10 at 2,465 points), so there are at most 256
-//     tiles; the tile's 28 sums are a tree over its points, stored k-major
-//     per level ([28][256]).
+//     tiles; the tile's 28 sums are a tree over its points, stored per level
+//     in the order the next launch loads them ([4 waves][16][56][2],
+//     partial_index; the continuation's and the rig's scratch k-major,
+//     [28][256]).
 // F (one workgroup): solves level 0 and writes the pose (+ pose log).
 //
-// The solve (one level, replicated in every workgroup): tile t's partials in
-// thread t, a canonical tree over the tiles (reduce-scatter per wave, then
-// the 4 waves); then on wave 0 alone: Eigen PartialPivLU of H replicated in
-// every lane's registers (direct_solve.hpp; the pivot row made wave-uniform),
+// The solve (one level, replicated in every workgroup): a canonical tree over
+// the <= 256 tile slots on waves 0-3, wave w the tiles 64 w .. 64 w + 63: lane
+// (g, s) loads sums 2 s and 2 s + 1 of the 16 tiles 64 w + 16 g .. + 15
+// (sixteen 16-byte loads, each one contiguous 896-byte run per wave) and adds
+// each sum's 16 tiles in its registers, four levels of the tree; two DPP
+// levels across g finish the wave, then (w0 + w1) + (w2 + w3)
+// (load_partials_tree16, reduce_tree16_pairs); then on wave 0 alone: Eigen
+// PartialPivLU of H replicated in every lane's registers (direct_solve.hpp;
+// the pivot row made wave-uniform),
 // the inverse with lane c solving column c, update = H^-1 b,
 // SE3::exp(update) * T21 (sin/cos of theta/2 and theta in two lanes at once),
 // cost / nGood and the checks of :741-753.  Every element sees the same operations in the same order as the
@@ -118,6 +125,9 @@ constexpr int kRigWaves = 16;
 constexpr int kRigThreads = kRigWaves * 64;
 constexpr int kMaxTiles = 256;
 constexpr int kMaxTile = kMaxMapPoints / kMaxTiles;  // 64 points
+// lanes of a wave that load and reduce level partials: 14 pairs of sums x 4
+// groups of 16 tiles (load_partials_tree16)
+constexpr int kTreeLanes = kSums / 2 * 4;
 
 // Points per tile of the canonical map tree (oracle_common.hpp map_tile):
 // min(64, max(1, ceil(n / groups))).
@@ -1146,13 +1156,13 @@ constexpr unsigned kSrcHere = 0xffffffffu;  // direct_tile_pf: factored_sources(
 
 // Where sum k of tile b lies in a level's partials.  k-major ([28][256]: the
 // continuation's and the rig's scratch, read by load_partials and the rig's
-// reader), or PAIRED ([14][4 waves][2][64]: sum k + 14 h of tile 64 w + j at
-// [k][w][h][j], the level scratch load_partials_paired reads).
+// reader), or PAIRED ([4 waves][16][56][2]: sums 2 s and 2 s + 1 of tile
+// 64 w + 16 g + j side by side at [w][j][4 s + g], the level scratch
+// load_partials_tree16 reads).
 template <bool PAIRED>
 __device__ inline size_t partial_index(int k, int b) {
     if (!PAIRED) return (size_t)k * kMaxTiles + b;
-    const int h = k >= kSums / 2 ? 1 : 0;
-    return (size_t)((((k - h * (kSums / 2)) * 4 + (b >> 6)) * 2 + h) * 64 + (b & 63));
+    return (size_t)((((b >> 6) * 16 + (b & 15)) * kTreeLanes + ((k >> 1) * 4 + ((b >> 4) & 3))) * 2 + (k & 1));
 }
 
 template <bool FAST, bool LV16 = false, int W = kWaves, bool PAIRED = false>
@@ -1297,32 +1307,29 @@ __device__ inline void load_partials(const double* __restrict__ part, const int*
     }
 }
 
-// The level scratch's loader, with the canonical tree's first level (tile 2 p
-// + tile 2 p + 1) taken in the load: the two tiles of one sum are neighbours,
-// so one 16-byte load brings both addends.  Lane p < 32 of wave w takes the
-// pair p of the wave's 64 tiles for sums 0..13, lane 32 + p the same pair for
-// sums 14..27: fourteen loads per lane instead of 28, and the level's selects
-// and DPP moves go (a + b == b + a bit for bit; a tile beyond n_tiles is the
-// +0.0 it was).  The PAIRED layout (partial_index) puts a wave's two halves
-// side by side, so each load instruction reads one contiguous 1 KB run (in
-// the k-major layout it was two 512-byte runs 14 * 2 KB apart).
-// a[14] feeds reduce_scatter_28_paired; gg stays tile t's count.
-__device__ inline void load_partials_paired(const double* __restrict__ part, const int* __restrict__ good,
-                                            int n_tiles, double* a, int& gg) {
-    const int t = threadIdx.x;
-    const int t0 = (t & ~63) + 2 * (t & 31);
-    if (t0 < n_tiles) {
-        const bool has1 = t0 + 1 < n_tiles;
-        // [k][w][h][j] with w = t >> 6, h = (t >> 5) & 1, j = 2 (t & 31): double 256 k + 2 t
-        const double2* __restrict__ p2 = reinterpret_cast<const double2*>(part) + t;
+// The level scratch's loader, with four levels of the canonical tree taken in
+// the loads: lane l < 56 of wave w is (g = l & 3, s = l >> 2) and takes sums
+// 2 s and 2 s + 1 of the 16 tiles 64 w + 16 g .. + 15, an index-aligned
+// subtree, which reduce_tree16_pairs then adds in registers.  Load j brings
+// both sums of tile 64 w + 16 g + j in 16 bytes; the PAIRED layout
+// (partial_index) puts the 56 lanes of one load instruction side by side, so
+// each of the sixteen instructions reads one contiguous 896-byte run.
+// A tile at or beyond n_tiles is not loaded: its register pair is set to the
+// +0.0 the tree pads with, per element and from this launch's n_tiles alone,
+// so nothing the scratch holds past the map's last tile (an earlier, larger
+// map's sums) is ever read, and the tree needs no selects behind the loads.
+// x[16] feeds reduce_tree16_pairs; gg stays tile t's count.
+__device__ inline void load_partials_tree16(const double* __restrict__ part, const int* __restrict__ good,
+                                            int n_tiles, double2* x, int& gg) {
+    const int t = threadIdx.x, lane = t & 63;
+    // tiles of this lane's 16 that the map has (lanes 56..63: none)
+    const int m = lane < kTreeLanes ? n_tiles - ((t & ~63) + 16 * (lane & 3)) : 0;
+    // [w][j][l][2] with w = t >> 6: double2 (16 w + j) * 56 + l
+    const double2* __restrict__ p2 = reinterpret_cast<const double2*>(part) + (size_t)(t >> 6) * 16 * kTreeLanes + lane;
 #pragma unroll
-        for (int k = 0; k < kSums / 2; ++k) {
-            const double2 x = p2[(size_t)k * kMaxTiles];
-            a[k] = x.x + (has1 ? x.y : 0.0);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kSums / 2; ++k) a[k] = 0.0;
+    for (int j = 0; j < 16; ++j) {
+        x[j] = make_double2(0.0, 0.0);
+        if (j < m) x[j] = p2[j * kTreeLanes];
     }
     gg = t < n_tiles ? good[t] : 0;
 }
@@ -1489,9 +1496,9 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
     // while the workgroup's waves arrive at the first barrier: the partials
     // of level sl (waves 0-3) and the T21 that level was evaluated at (thread
     // 256; every prefetch wave for its prediction)
-    double v[kSums / 2];  // the tree's first level is taken in the load
+    double2 v[16];  // two sums of 16 tiles: four levels of the tree are taken in the loads
     int gg = 0;
-    if (((pre_hdr >> 16) & 1) && t < 256) load_partials_paired(pre_part, pre_good, pre_hdr & 0xffff, v, gg);
+    if (((pre_hdr >> 16) & 1) && t < 256) load_partials_tree16(pre_part, pre_good, pre_hdr & 0xffff, v, gg);
     const bool pf_wave = !solve || (wave & 3) != 0;
     double st[7];
     if (t == 256 || (solve && tiles && pf_wave)) {
@@ -1536,9 +1543,9 @@ __global__ __launch_bounds__(kThreads, 4) void direct_level_kernel(const double*
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (wave == 0) PST(17);
 #endif
-        int idx;
-        const double f = reduce_scatter_28_paired(v, &idx);
-        if (!(lane & 16) && idx >= 0) L.red[wave][idx] = f;
+        // lane (g, s) ends with sum 2 s + (g & 1) of the wave's 64 tiles
+        const double f = reduce_tree16_pairs(v);
+        if (lane < kTreeLanes && !(lane & 2)) L.red[wave][2 * (lane >> 2) + (lane & 1)] = f;
         const int g = wave_sum_int(gg);
         if (lane == 0) L.g[wave] = g;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -568,7 +568,7 @@ constexpr int kMaxMapPoints = 16384;
 // Device scratch of the direct pose (carved from one buffer of
 // direct_scratch_bytes() by direct_scratch_at).
 struct DirectScratch {
-    double* part = nullptr;       // [kLevels][14][4][2][64] tile partial sums (direct.hip partial_index)
+    double* part = nullptr;       // [kLevels][4][16][56][2] tile partial sums (direct.hip partial_index)
     int* good = nullptr;          // [kLevels][256]
     double* state = nullptr;      // [kLevels + 1][8] T21 per level (+ result)
     double* cont_part = nullptr;  // [256 workgroups][256][28] continuation scratch
